@@ -1,6 +1,6 @@
 """bench.py — denoise-step throughput of the quantized SD1.4 / SDXL UNet on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5] [--dump-outputs DIR] [--full]
 
 N > 1 without a torchrun environment: the parent process — before anything touches the GPU — checks that N devices
 are visible (fails loudly otherwise) and starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
@@ -17,16 +17,20 @@ scripts/quantize_act.sh:16-19).  Inputs are resident in HBM when the timed regio
   c4 = SDXL-turbo W4A8 g16, 1024² (128² latents), batch 1, 4-step schedule, no CFG (BASELINE.json configs[3])
   c5 = SDXL-turbo W4A6 g=1 (scalar scales, uniform softmax quantiser), 8 prompts per GPU (configs[4]: 64 prompts / 8 GPUs)
 
-Timing: W untimed warm-up steps, then `--windows` (default 5) windows of EXACTLY K steps, each bracketed by a barrier +
-torch.cuda.synchronize() on both sides, max over ranks per window; `value` / `ms_per_step` come from the MEDIAN window,
-the minimum and every window are printed beside it.
+Timing: W untimed warm-up steps, then ONE window of EXACTLY K steps, bracketed by a barrier + torch.cuda.synchronize() on
+both sides, max over ranks; `value` / `ms_per_step` come from it.  With `--full`, `--windows` (default 5) windows of K steps
+each: `value` / `ms_per_step` come from the MEDIAN window, the minimum and every window are printed beside it.
 
-The JSON line also carries
+--dump-outputs DIR: after the timed steps, what the last timed step returned to its caller (the updated latents of rank 0,
+float32) is written as DIR/latents.npy.  Inputs and weights are seeded: the same arguments give the same inputs.
+
+A plain run does only what the headline needs (set up, warm up, time, dump, print).  `--full` adds the rest of the line:
   roofline     — the W4A8 MFMA GEMM path (dgq_gemm_wxa8): algorithmic int8 ops of all quantized layers of one step
                  (2·M·N·K, SURVEY.md §8(d): 1.354 Top for c2) ÷ the HIP-event time of those launches, against the
                  dense int8 MFMA peak (≈5 Pop/s = 2× the 2.5 PF bf16 peak, MI355X_MICROARCH.md § Matrix cores);
   cpu_baseline — the reference's op sequence (oracle/, a pinned CPU port: re-quantised weights each call, F.unfold,
-                 fp32 GEMMs, materialised attention) on this box's host cores: 1 warm-up + 3 timed steps (c2 only).
+                 fp32 GEMMs, materialised attention) on this box's host cores: 1 warm-up + 3 timed steps (c2 only);
+  non_hip_kernels — the static kernel-class record of profiles/ for this configuration.
 """
 import argparse
 import json
@@ -77,12 +81,17 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of --steps steps each (median reported)")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="timed windows of --steps steps each (median reported); default 1, or 5 with --full")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline replay pass, the CPU baseline, the static kernel-class record and 5 timed windows")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0's latents, float32) as DIR/latents.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline", action="store_true", help="force the CPU leg for c4/c5 too (minutes per SDXL step)")
+    ap.add_argument("--cpu-baseline", action="store_true", help="(--full) force the CPU leg for c4/c5 too (minutes per SDXL step)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of one hipGraph per timestep slot")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the per-launch GEMM replay pass (profiling runs)")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) skip the per-launch GEMM replay pass (profiling runs)")
     ap.add_argument("--prompts-per-gpu", type=int, default=0,
                     help="prompts denoised together on each GPU (default: the config's own: c2/c4 1, c5 8)")
     ap.add_argument("--dev-no-guidance", action="store_true",
@@ -90,7 +99,12 @@ def parse_args(argv=None):
                          "config.workload / config.dev_override and is never the headline")
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "fp16", "bf16"],
                     help="inter-layer activation dtype (fp32 = the reference's default .float() mode)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.cpu_baseline and not args.full:
+        ap.error("--cpu-baseline is part of --full")
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
+    return args
 
 
 def launch_command(args, argv, port):
@@ -140,6 +154,55 @@ class _FpDryModel:
         return self.unet(x, torch.tensor(int(t)), encoder_hidden_states=ctx)
 
 
+def _act_slots(job):
+    """worker of write_synthetic_ckpt: the act_<s> tables of some slots (each drawn from name-keyed generators), serialised
+    (thousands of small tensors: torch's fd-passing of tensors between processes runs out of descriptors)"""
+    import io
+    import torch
+    from dgq_amd import synth
+    arch, bits, G, slots, batch, res, sp, uniform, recs = job
+    with synth._one_thread():
+        tables = [synth.synth_act_slot(arch, bits, G, s, 0, batch, res, sp, uniform, recs) for s in slots]
+    buf = io.BytesIO()
+    torch.save(tables, buf)
+    return buf.getvalue()
+
+
+def write_synthetic_ckpt(arch, qcfg, res, batch, n_slots, ckpt_dir="/tmp", workers=12):
+    """Writes the synthetic cali_ckpt that dgq_amd.runtime.synthetic_fp_unet would write at its first use (same file name, same
+    tensors bit for bit: every table is drawn from name-keyed generators), the per-slot activation tables in ``workers`` spawned
+    processes and the weights meanwhile in this one: 50 slots of SD tables take 17 s on one host thread.  Returns the path; an
+    existing file is kept."""
+    import io
+    import multiprocessing
+    from collections import OrderedDict
+    import torch
+    from dgq_amd import synth
+    path = os.path.join(ckpt_dir, "dgq_synth_%s_w%da%dg%d_r%d_b%d_s%d_%s.pth" % (
+        arch, qcfg["wbits"], qcfg["abits"], qcfg["G"], res, batch, n_slots, "sp" if qcfg["sp"] else "nosp"))
+    if os.path.exists(path):
+        return path
+    ck = OrderedDict()
+    if qcfg["use_aq"]:
+        recs = synth.enumerate_act_quantizers(arch, batch, res)
+        uniform = qcfg["use_aq"] and not qcfg["log"]
+        nw = max(1, min(workers, n_slots))
+        jobs = [(arch, qcfg["abits"], qcfg["G"], list(range(i, n_slots, nw)), batch, res, qcfg["sp"], uniform, recs) for i in range(nw)]
+        with multiprocessing.get_context("spawn").Pool(nw) as pool:      # (a fork would inherit torch's used OpenMP pool)
+            pending = pool.map_async(_act_slots, jobs)
+            weight = synth.synth_weight_ckpt(arch, qcfg["wbits"], 0, False)
+            parts = [torch.load(io.BytesIO(b)) for b in pending.get()]
+        for s in range(n_slots):
+            ck["act_%d" % s] = parts[s % nw][s // nw]
+    else:
+        weight = synth.synth_weight_ckpt(arch, qcfg["wbits"], 0, False)
+    ck["weight"] = weight
+    tmp = path + ".tmp%d" % os.getpid()
+    torch.save(ck, tmp)
+    os.replace(tmp, path)
+    return path
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
@@ -159,6 +222,28 @@ def main(argv=None):
         return 2
     dist = None
     DRY = dry_run()
+    C = CONFIGS[args.config]
+    arch, res, qcfg, guidance = C["arch"], C["res"], C["cfg"], C["guidance"]
+    if args.dev_no_guidance:                                 # development: the conditional half alone (batch 1); labelled in the line below
+        guidance = 0.0
+    if DRY:
+        arch, res, guidance = "tiny", 16, 7.5
+        args.no_graph = args.no_roofline = args.no_cpu_baseline = True
+    K, W = args.steps, args.warmup
+    P = args.prompts_per_gpu or C["prompts"]
+    nsteps = qcfg["steps"]
+    from dgq_amd.runtime import DDIMScheduler
+    sch = DDIMScheduler(nsteps)
+    sched_ts = sch.timesteps if arch in ("sd", "tiny") else [999, 749, 499, 249]     # SDXL-turbo: src/inference_qmodel.py:49-54 trailing spacing
+    n_ts = min(K + W, len(sched_ts))
+    timesteps = [sched_ts[i % n_ts] for i in range(W + K)]
+    slots = sorted({(1000 - t) // (1000 // nsteps) for t in timesteps})
+    batch = (2 if guidance > 0 else 1) * P
+    t_model = time.perf_counter()
+    write_s = None
+    if not DRY and rank == 0:                                # the synthetic ckpt's tables in parallel (the runtime would write it serially)
+        write_synthetic_ckpt(arch, qcfg, res, batch, max(slots) + 1)
+        write_s = time.perf_counter() - t_model
     if not DRY:
         torch.cuda.set_device(local_rank)
     # host-side work of the load (planning, packing tables, the synthetic ckpt): a GPU box shows every host thread but grants a
@@ -173,7 +258,7 @@ def main(argv=None):
     dev = torch.device("cpu") if DRY else torch.device("cuda", local_rank)
 
     from dgq_amd import ops, synth
-    from dgq_amd.runtime import build_synthetic_qnn, synthetic_fp_unet, DDIMScheduler
+    from dgq_amd.runtime import build_synthetic_qnn, synthetic_fp_unet
     from dgq_amd._lib import require_gpu
     if not DRY:
         require_gpu()
@@ -186,23 +271,6 @@ def main(argv=None):
         if dist is not None:
             dist.barrier()
 
-    C = CONFIGS[args.config]
-    arch, res, qcfg, guidance = C["arch"], C["res"], C["cfg"], C["guidance"]
-    if args.dev_no_guidance:                                 # development: the conditional half alone (batch 1); labelled in the line below
-        guidance = 0.0
-    if DRY:
-        arch, res, guidance = "tiny", 16, 7.5
-        args.no_graph = args.no_roofline = args.no_cpu_baseline = True
-    K, W = args.steps, args.warmup
-    P = args.prompts_per_gpu or C["prompts"]
-    nsteps = qcfg["steps"]
-    sch = DDIMScheduler(nsteps)
-    sched_ts = sch.timesteps if arch in ("sd", "tiny") else [999, 749, 499, 249]     # SDXL-turbo: src/inference_qmodel.py:49-54 trailing spacing
-    n_ts = min(K + W, len(sched_ts))
-    timesteps = [sched_ts[i % n_ts] for i in range(W + K)]
-    slots = sorted({(1000 - t) // (1000 // nsteps) for t in timesteps})
-    batch = (2 if guidance > 0 else 1) * P
-    t_model = time.perf_counter()
     if DRY:
         unet, ckpt_path, laps, _ = synthetic_fp_unet(arch, qcfg, res, batch, max(slots) + 1, ckpt_dir=os.environ.get("DGQ_BENCH_CKPT_DIR", "/tmp"),
                                                      rank=rank, barrier=barrier)
@@ -290,6 +358,10 @@ def main(argv=None):
                 el = float(tt.item())
             windows.append(el)
     assert torch.isfinite(x).all()
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "latents.npy"), x.detach().float().cpu().numpy())
     elapsed = statistics.median(windows)
     ready_per_rank = [round(model_ready_s, 1)]
     if dist is not None:                   # every rank's load time (they run concurrently; rank 0 also writes the ckpt)
@@ -304,12 +376,12 @@ def main(argv=None):
     # per-launch events would time the host-side launch gaps, not the kernels.  Sum over the step = the kernel time
     # rocprofv3 reports for the GEMM kernels (profiles/).
     roofline, roofline_extra = None, {}
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         roofline, roofline_extra = measure_gemm_roofline(torch, ops, qnn, lambda: one_step(lat, timesteps[W]), args)
 
     # ---- CPU baseline: the reference's op sequence (oracle port) on this box's host cores ----------------------------
     cpu_baseline = None
-    want_cpu = (args.config == "c2" and not args.no_cpu_baseline) or args.cpu_baseline
+    want_cpu = args.full and ((args.config == "c2" and not args.no_cpu_baseline) or args.cpu_baseline)
     if rank == 0 and world == 1 and want_cpu:
         from oracle import dgq_oracle as orc
         ck = torch.load(ckpt_path, map_location="cpu")
@@ -357,7 +429,8 @@ def main(argv=None):
         # stamped with the commit it was measured at
         glue = None
         import glob
-        for gj in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_step_kernel_classes.json")), reverse=True):
+        records = glob.glob(os.path.join(ROOT, "profiles", "r*_step_kernel_classes.json")) if args.full else []
+        for gj in sorted(records, reverse=True):
             gd = json.load(open(gj))
             if (gd.get("config") == args.config and gd.get("dtype") == args.dtype and gd.get("graph", True) == (not args.no_graph)
                     and (args.prompts_per_gpu or C["prompts"]) == C["prompts"]):
@@ -374,6 +447,8 @@ def main(argv=None):
             overrides.append("--dev-no-guidance: conditional half only, batch %d" % batch)
             workload_label = workload_label.replace("CFG pair per step per GPU", "NO CFG pair: conditional half only (development run)")
         load = dict(getattr(qnn, "_build_laps", {}))
+        if write_s is not None:
+            load["write cali_ckpt"] = round(write_s, 2)
         load.update({"prepare_slots (plan + pack %d slots)" % len(slots): round(t_prep, 2),
                      "model_ready_s": round(sum(v for k, v in load.items() if k != "write cali_ckpt") + t_prep, 1),
                      "note": "model_ready_s = FP UNet + weights + get_qmodel (wrap, load_cali_model) + prepare_slots; the "

@@ -12,6 +12,7 @@
     python tests/golden/make_golden.py ddim_traj [steps] [res]   # F5b every call of that run: ε output + the call's self-deviation
     python tests/golden/make_golden.py pndm | euler     # F7 vendored PNDM / EulerAncestral schedulers on a closed-form ε model
     python tests/golden/make_golden.py pndm_unet [steps] [res]   # F10 the reference QuantModel under the pipeline's PNDM loop
+    python tests/golden/make_golden.py dropin           # F11 the reference SD UNet's module tree + its bare FP output, 16x16
     DIFFUSERS_REWRITE=sdxl python tests/golden/make_golden.py unet xl   # SDXL (separate process)
     DIFFUSERS_REWRITE=sdxl python tests/golden/make_golden.py unet xl_c5 32   # SDXL W4A6 g=1 (config C5), 32x32 latents; xl_c5b8: 8 prompts
 
@@ -418,6 +419,17 @@ def make_schema(ref, arch):
                        act0=schema["act_0"], weight={k: v for k, v in list(schema["weight"].items())},
                        loader_side_effects=side, slots=slots), f)
     print("wrote schema", arch)
+
+
+def make_dropin(ref):
+    """F11: what the drop-in test needs from the reference's own UNet classes: the module tree of the SD UNet (qualified name,
+    class name) and the bare floating-point output on the seeded synthetic weights and inputs (t = 981, 16x16 latents)."""
+    torch.manual_seed(0)
+    unet = ref.dr.UNet2DConditionModel()
+    unet.load_state_dict(synth.synth_state_dict("sd", 0))
+    inp = synth.synth_inputs("sd", 2, 1, 16)
+    y = unet(inp["sample"], torch.tensor(981), inp["encoder_hidden_states"])[0].clone()
+    save("f11_dropin_sd_r16.pt", dict(t=981, res=16, batch=2, modules=[(n, type(m).__name__) for n, m in unet.named_modules()], y=y))
 
 
 # --------------------------------------------------------------------------------------- calibration producer (f1)
@@ -880,6 +892,8 @@ if __name__ == "__main__":  # noqa: C901
         make_layers_wide(ref)
     elif what == "schema":
         make_schema(ref, arch)
+    elif what == "dropin":
+        make_dropin(ref)
     elif what == "unet":
         res = int(sys.argv[3]) if len(sys.argv) > 3 else None
         make_unet(ref, arch, sys.argv[2], res=res)

@@ -344,8 +344,8 @@ def test_bench_two_rank_dry_run_under_gloo(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, DGQ_BENCH_BACKEND="gloo", DGQ_BENCH_CKPT_DIR=str(tmp_path), OMP_NUM_THREADS="2")
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--windows", "2"],
-                       capture_output=True, text=True, timeout=600, env=env)
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--windows", "2",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -356,6 +356,39 @@ def test_bench_two_rank_dry_run_under_gloo(tmp_path):
     assert d["config"]["parallelism"].startswith("replicas x2")
     files = [f for f in os.listdir(tmp_path) if f.endswith(".pth")]
     assert len(files) == 1                                   # one ckpt, written by rank 0 only
+    import numpy as np
+    lat = np.load(tmp_path / "out" / "latents.npy")          # --dump-outputs: rank 0's latents after the last timed step
+    assert lat.dtype == np.float32 and lat.shape == (1, 4, 16, 16) and np.isfinite(lat).all()
+
+
+@pytest.mark.parametrize("config", ["c2", "c5"])
+def test_bench_synthetic_ckpt_writer_is_the_runtime_one(config, tmp_path):
+    """bench.write_synthetic_ckpt (activation tables drawn in forked workers) writes the file dgq_amd.runtime would write at its
+    first use: same name (the runtime finds it and does not rewrite it) and the same tensors, bit for bit."""
+    import bench
+    from dgq_amd.runtime import synthetic_fp_unet
+    cfg = bench.CONFIGS[config]["cfg"]
+    path = bench.write_synthetic_ckpt("tiny", cfg, 16, 2, 5, ckpt_dir=str(tmp_path), workers=3)
+    mtime = os.path.getmtime(path)
+    _, path2, _, _ = synthetic_fp_unet("tiny", cfg, 16, 2, 5, ckpt_dir=str(tmp_path))
+    assert path2 == path and os.path.getmtime(path) == mtime
+    a = torch.load(path)
+    b = synth.build_cali_ckpt("tiny", cfg["wbits"], cfg["abits"], cfg["G"], 5, 0, 2, 16, cfg["sp"], not cfg["log"], False, True)
+    assert list(a) == list(b) == ["act_%d" % s for s in range(5)] + ["weight"]
+    for part in b:
+        assert list(a[part]) == list(b[part]) and all(torch.equal(a[part][k], b[part][k]) for k in b[part]), part
+
+
+def test_bench_plain_run_times_steps_once_and_full_adds_the_rest():
+    """A plain run times ONE window of --steps steps and nothing else; --full brings back the 5 windows (the roofline pass and the
+    CPU baseline are gated on it in main())."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.windows == 1 and not a.full and a.dump_outputs is None
+    f = bench.parse_args(["--steps", "7", "--full", "--dump-outputs", "d"])
+    assert f.full and f.windows == 5 and f.dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--cpu-baseline"])
 
 
 def test_skip_concatenation_in_place_host_logic():

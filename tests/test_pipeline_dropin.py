@@ -1,7 +1,7 @@
 """SURVEY.md §8(f)-3 — the caller side of the drop-in: the diffusers pipeline loop (restated in dgq_amd/pipeline.py; HF
-diffusers itself is not installed), PNDM's N+1-call schedule and its slot aliasing, and the reference's OWN UNet classes
-wrapped by this package's QuantModel / load_cali_model (duck-typing; dev container only — /root/reference does not
-travel)."""
+diffusers itself is not installed), PNDM's N+1-call schedule and its slot aliasing, and a UNet built module for module like the reference's OWN UNet
+classes (their tree and output recorded in tests/golden/f11_dropin_sd_r16.pt) wrapped by this package's QuantModel /
+load_cali_model (duck-typing)."""
 import os
 import types
 
@@ -112,24 +112,28 @@ def test_quantmodel_under_the_pndm_pipeline_loop(tmp_path):
     assert e < 1e-5, e
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/quant"), reason="the reference is mounted in the build container only")
 def test_reference_unet_classes_are_wrapped_by_duck_typing(tmp_path):
-    """INTEGRATION.md's claim, executed: the REFERENCE's diffusers_rewrite.UNet2DConditionModel (its Attention /
-    BasicTransformerBlock / ResnetBlock2D classes) goes through THIS package's QuantModel + load_cali_model:
+    """INTEGRATION.md's claim, executed: a UNet laid out like the REFERENCE's diffusers_rewrite.UNet2DConditionModel — every
+    module whose class the surgery keys on (Conv2d / Linear, BasicTransformerBlock / ResnetBlock2D) at the same qualified name
+    with the same class name as in the reference's module tree, which make_golden.py `dropin` recorded in F11; the stage
+    containers may differ — goes through THIS package's QuantModel + load_cali_model:
     same module surgery counts as the reference's QuantModel (282 QuantLayer, 16 + 22 Quant blocks), every ckpt key
     loads, loader side effects as fixture F6, and — in the floating-point state, which runs on CPU — the wrapped model
-    reproduces the bare reference UNet's output."""
+    reproduces the bare reference UNet's output (F11)."""
     import json
-    from oracle import ref_harness as rh
-    ref = rh.import_reference("sd")
+    from dgq_amd.diffusers_rewrite import UNet2DConditionModel
     from dgq_amd.quant import QuantModel, QuantLayer, Scaler, load_cali_model
     from dgq_amd.quant.quant_block import QuantBasicTransformerBlock, QuantResnetBlock2D
+    from dgq_amd.quant.quant_model import b2qb
+    g = torch.load(os.path.join(GOLD, "f11_dropin_sd_r16.pt"))
     torch.manual_seed(0)
-    unet = ref.dr.UNet2DConditionModel()
+    unet = UNet2DConditionModel("sd")
+    keyed = set(b2qb()) | {c.__name__ for c in QuantLayer.QMAP}
+    tree = [(n, type(m).__name__) for n, m in unet.named_modules() if type(m).__name__ in keyed]
+    assert tree == [tuple(e) for e in g["modules"] if e[1] in keyed] and len(tree) == 320
     unet.load_state_dict(synth.synth_state_dict("sd", 0))
     inp = synth.synth_inputs("sd", 2, 1, 16)
-    with torch.no_grad():
-        y_ref = unet(inp["sample"], torch.tensor(981), inp["encoder_hidden_states"])[0].clone()
+    y_ref = g["y"]
     wq = {"bits": 4, "channel_wise": True, "scaler": Scaler.MINMAX}
     aq = {"bits": 8, "channel_wise": False, "scaler": Scaler.MINMAX, "leaf_param": True}
     sm = {"softmax_a_bit": 8, "t2i_log_quant": True, "t2i_real_time": True, "t2i_start_peak": True, "log_max_1": False}
@@ -139,7 +143,7 @@ def test_reference_unet_classes_are_wrapped_by_duck_typing(tmp_path):
     n_rb = sum(isinstance(m, QuantResnetBlock2D) for m in qnn.modules())
     assert (n_layers, n_tb, n_rb) == (282, 16, 22)
     assert qnn.config.in_channels == 4 and qnn.config.sample_size == 64 and qnn.config.time_cond_proj_dim is None
-    # floating-point state: the Quant blocks' glue around the reference's own submodules
+    # floating-point state: the Quant blocks' glue around the UNet's own submodules
     qnn.set_quant_state(False, False)
     with torch.no_grad():
         y = qnn(inp["sample"], torch.tensor(981), inp["encoder_hidden_states"], timestep_cond=None,

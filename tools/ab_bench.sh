@@ -7,7 +7,7 @@ i=0
 for envs in "$@"; do
   i=$((i+1))
   out=gpurun_out/ab_$i.json
-  env $envs python bench.py --no-cpu-baseline ${BENCH_ARGS:-} > $out 2> gpurun_out/ab_$i.err || { tail -5 gpurun_out/ab_$i.err; exit 1; }
+  env $envs python bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} > $out 2> ${out%.json}.err || { tail -5 ${out%.json}.err; exit 1; }
   python - "$envs" $out <<'PY'
 import json, sys
 line = [l for l in open(sys.argv[2]) if l.startswith("{")][-1]

@@ -4,7 +4,7 @@
 #   tools/final_evidence.sh <tag> <commit>   -> gpurun_out/<tag>/*   (the traffic records are stamped with the digest of the kernel sources)
 TAG=${1:-r05z}; COMMIT=${2:-unknown}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
-python bench.py > $O/bench_line.json 2> $O/bench.err; tail -c 600 $O/bench_line.json
+python bench.py --full > $O/bench_line.json 2> $O/bench.err; tail -c 600 $O/bench_line.json
 python tools/bench_attn.py 2>&1 | grep -v amdgpu.ids > $O/attention_shapes.txt; cat $O/attention_shapes.txt
 cd /tmp; export TMPDIR=/tmp
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --steps 2 --warmup 1 --no-graph --no-cpu-baseline --no-roofline --windows 1 > $O/pmc_fetch.log 2>&1
