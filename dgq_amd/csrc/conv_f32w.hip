@@ -3,8 +3,10 @@
 // that to F.linear / F.conv2d).  Integer MFMA does not apply — the activations are fp32 — so this is an exact-fp32 GEMM on
 // V_MFMA_F32_32X32X2_F32 (each product and add as in an fmaf chain) with the convolution's im2col folded into the A-tile
 // load: rows = output positions, K = tap·C + c (natural order), out-of-image taps read 0 like F.conv2d's zero padding.
-// Plumbing-grade tiling (64x64 block tile, 16-deep K tiles through LDS, no ring): this state is not on the timed path; it
-// exists so that no state of a quantized model leaves this library on the GPU.
+// Plumbing-grade tiling (64x64 block tile, 16-deep K tiles through LDS, no ring): it serves the FP state (conv_in / conv_out of a
+// quantized model), the weight-only layers with N <= 8 and QuantLayer.WEIGHT_ONLY_PACKED = False; the weight-only layers with N > 8
+// run on gemm_wonly.hip from their packed codes — bit for bit this kernel's result on the dequantised weight, whose chain (from +0.0f,
+// k in order, +0 products up to the next multiple of CF_BK, then + bias) that kernel reproduces.
 #include "quant_common.h"
 
 typedef float v16f __attribute__((ext_vector_type(16)));

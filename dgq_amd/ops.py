@@ -999,6 +999,39 @@ def conv2d_f32w(x: torch.Tensor, w_nat: torch.Tensor, bias, kh, kw, stride, pad,
     return y.view(*x.shape[:-1], N)
 
 
+def conv2d_wq(x: torch.Tensor, pw: PackedWeight, kh, kw, stride, pad, upsample=False, geglu_rows=False):
+    """Weight-only state from the packed codes (dgq_conv2d_wq): bit for bit ``conv2d_f32w(x, δ·(q − z) in natural order, pw.bias)``,
+    without an fp32 copy of the weight — each element is dequantised as the kernel stages it.  Inputs and returned views as in
+    conv2d_f32w: x logical NCHW (made channels-last) or [..., K] for a Linear layer (kh = kw = 1).  ``upsample``: the layer sees
+    F.interpolate(x, scale_factor=2, mode="nearest"), read through the (h/2, w/2) mapping and never written.  ``geglu_rows``: pw's
+    rows are interleaved (QuantLayer.geglu_rows) and the output comes back in the reference's column order.  N > 8."""
+    w_img, Kp = pw.natural()
+    N = pw.N
+    is_conv = x.dim() == 4 and pw.K == kh * kw * x.shape[1]
+    if is_conv:
+        B, C, H, W = x.shape
+        if upsample:
+            H, W = 2 * H, 2 * W
+        xs = x.contiguous(memory_format=torch.channels_last)
+        Ho = (H + 2 * pad - kh) // stride + 1
+        Wo = (W + 2 * pad - kw) // stride + 1
+        y = torch.empty((B * Ho * Wo, N), dtype=x.dtype, device=x.device)
+        _lib_call("dgq_conv2d_wq", _lib.ptr(xs), _lib.DTYPE_CODE[x.dtype], B, H, W, C, kh, kw, stride, pad, int(upsample),
+                  _lib.ptr(w_img), pw.bits, Kp, _lib.ptr(pw.alpha), _lib.ptr(pw.zp_true), _lib.ptr(pw.bias), N, int(geglu_rows),
+                  _lib.ptr(y), _lib.DTYPE_CODE[y.dtype], N, _lib.stream())
+        return y.view(B, Ho, Wo, N).permute(0, 3, 1, 2)
+    K = x.shape[-1]
+    assert pw.K == K and kh == kw == 1 and not upsample, "dgq conv2d_wq: weight [N][%d] does not match input %s" % (pw.K, tuple(x.shape))
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    y = torch.empty((x2.shape[0], N), dtype=x.dtype, device=x.device)
+    _lib_call("dgq_conv2d_wq", _lib.ptr(x2), _lib.DTYPE_CODE[x.dtype], x2.shape[0], 1, 1, K, 1, 1, 1, 0, 0,
+              _lib.ptr(w_img), pw.bits, Kp, _lib.ptr(pw.alpha), _lib.ptr(pw.zp_true), _lib.ptr(pw.bias), N, int(geglu_rows),
+              _lib.ptr(y), _lib.DTYPE_CODE[y.dtype], N, _lib.stream())
+    return y.view(*x.shape[:-1], N)
+
+
 # ------------------------------------------------------------------------------------------ attention side
 def fakequant_rows(x2d: torch.Tensor, T, D, mode, delta, zp, skip, bits, out=None):
     """x2d [rows][C] contiguous; see dgq_fakequant_rows."""

@@ -377,6 +377,9 @@ class UniformAffineQuantizer(nn.Module):
 LAYER_TAP = None
 #: weight-only state on the library's own exact-fp32 kernel (dgq_conv2d_f32w); =0: F.linear / F.conv2d on the dequantised weight
 WEIGHT_ONLY_HIP = True
+#: ... computed from the packed W4 / W8 codes (dgq_conv2d_wq: the same bits, no fp32 copy of the weight) for every layer with N > 8;
+#: False: dgq_conv2d_f32w on dequantized_weight_natural()
+WEIGHT_ONLY_PACKED = True
 #: ... and the FP state (unquantised layers: conv_in / conv_out of a quantized model) too, outside autograd; =0: MIOpen / rocBLAS
 FP_STATE_HIP = True
 
@@ -585,8 +588,13 @@ class QuantLayer(nn.Module):
             else:
                 if (WEIGHT_ONLY_HIP and x.dtype in ops.FLOAT_DTYPES and not (torch.is_grad_enabled() and x.requires_grad)
                         and (not self.is_conv or (tuple(self.fwd_kwargs.get("dilation", (1, 1)))[0] == 1 and self.fwd_kwargs.get("groups", 1) == 1))):
-                    # inference in the weight-only state: exact-fp32 MFMA kernel of this library (dgq_conv2d_f32w), not
-                    # F.linear / F.conv2d of the vendor libraries
+                    # inference in the weight-only state: exact-fp32 MFMA kernel of this library, not F.linear / F.conv2d of the
+                    # vendor libraries — from the packed codes (dgq_conv2d_wq), or on the dequantised fp32 weight (dgq_conv2d_f32w)
+                    if WEIGHT_ONLY_PACKED and self.w.shape[0] > 8:
+                        if self.is_conv:
+                            return ops.conv2d_wq(x, self.packed_weight(), self.w.shape[2], self.w.shape[3], self.fwd_kwargs["stride"][0],
+                                                 self.fwd_kwargs["padding"][0], geglu_rows=self.geglu_rows)
+                        return ops.conv2d_wq(x, self.packed_weight(), 1, 1, 1, 0, geglu_rows=self.geglu_rows)
                     wn, bn = self.dequantized_weight_natural()
                     if self.is_conv:
                         return ops.conv2d_f32w(x, wn, bn, self.w.shape[2], self.w.shape[3], self.fwd_kwargs["stride"][0],
@@ -649,7 +657,12 @@ class QuantLayer(nn.Module):
         """``self(F.interpolate(x, scale_factor=2.0, mode="nearest"))`` — Upsample2D.forward (diffusers_rewrite/sd.py).  On the integer
         path of a k x k convolution the quantise-on-load pass reads x through the (h/2, w/2) mapping and the upsampled tensor is
         never written (ops.quant_conv2d(upsample=True)); with a layer tap installed, during calibration or in any other state the
-        interpolate runs as written."""
+        interpolate runs as written.  In the weight-only state the packed-code kernel reads x through the same mapping
+        (ops.conv2d_wq(upsample=True)), under the same conditions."""
+        if (LAYER_TAP is None and self.is_conv and self.on_packed_weight_only_path(x) and not self.aqtizer.calibrating()
+                and not self._forward_hooks and not self._forward_pre_hooks):
+            return ops.conv2d_wq(x, self.packed_weight(), self.w.shape[2], self.w.shape[3], self.fwd_kwargs["stride"][0],
+                                 self.fwd_kwargs["padding"][0], upsample=True)
         if (LAYER_TAP is None and self.is_conv and self.on_integer_path(x) and x.dtype in ops.FLOAT_DTYPES and not self.aqtizer.calibrating()
                 and not self._forward_hooks and not self._forward_pre_hooks and self.w.shape[2] * self.w.shape[3] > 1):
             kh, kw = self.w.shape[2], self.w.shape[3]
@@ -657,6 +670,13 @@ class QuantLayer(nn.Module):
             return ops.quant_conv2d(x, self._binding(), kh, kw, self.fwd_kwargs["stride"][0], self.fwd_kwargs["padding"][0], upsample=True,
                                     out=out, out2=out2)
         return self(F.interpolate(x, scale_factor=2.0, mode="nearest"))
+
+    def on_packed_weight_only_path(self, x: torch.Tensor) -> bool:
+        """True when forward(x) would run dgq_conv2d_wq (weight-only state from the packed codes, GPU, outside autograd)."""
+        return (WEIGHT_ONLY_HIP and WEIGHT_ONLY_PACKED and self.use_wq and not (self.use_aq and not self.disable_aq) and x.is_cuda
+                and x.dtype in ops.FLOAT_DTYPES and not getattr(self.wqtizer, "soft_tgt", False)
+                and not (torch.is_grad_enabled() and x.requires_grad) and self.w.shape[0] > 8
+                and (not self.is_conv or (tuple(self.fwd_kwargs.get("dilation", (1, 1)))[0] == 1 and self.fwd_kwargs.get("groups", 1) == 1)))
 
     def on_integer_path(self, x: torch.Tensor) -> bool:
         """True when forward(x) would run dgq_quant_act + dgq_gemm_wxa8 (weights and activations quantised, GPU)."""

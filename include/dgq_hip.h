@@ -41,8 +41,9 @@ extern "C" {
  *        stride, pad; dgq_gemm_conv_act_fuses
  *   121  round 6: dgq_cfg_ddim_step takes the tensors' dtype (void pointers + `dtype`); dgq_attention_workspace_bytes grew by one fp32
  *        part area (key-split launches on 16-bit tensors)
- *   122  round 6: dgq_gemm_extra_t += y2, ldy2; dgq_conv2d_f32w takes y2 / ldy2 / gn_partial */
-#define DGQ_ABI_VERSION 122
+ *   122  round 6: dgq_gemm_extra_t += y2, ldy2; dgq_conv2d_f32w takes y2 / ldy2 / gn_partial
+ *   123  dgq_conv2d_wq (the weight-only state from the packed W4 / W8 codes) */
+#define DGQ_ABI_VERSION 123
 int dgq_version(void);
 const char* dgq_last_error(void);
 
@@ -180,6 +181,17 @@ int dgq_cfg_ddim_step(const void* eps_uncond, const void* eps_cond, const void* 
 int dgq_conv2d_f32w(const void* x, int x_dtype, int B, int H, int W, int C, int kh, int kw, int stride, int pad,
                     const float* w, const float* bias, int N, void* y, int y_dtype, int ldy,
                     const float* pre_scale, const float* pre_shift, int pre_act, void* y2, int ldy2, float* gn_partial, void* stream);
+
+/* dgq_conv2d_wq: the same layer computed from the packed weight, bit for bit what dgq_conv2d_f32w returns on the dequantised weight
+ * (N > 8).  w_packed is the natural-order image of PackedWeight.natural(): K in (tap, c) order padded to Kp (a multiple of
+ * DGQ_KTILE, >= kh·kw·C); w_bits 4 = dgq_pack_w4 layout 1, 8 = dgq_pack_w8 (int8 code − 128).  Every element is dequantised once,
+ * as it is staged, to ŵ = delta[n]·((float)q − zp[n]); bias [N] or NULL.  upsample = 1: x holds (H/2) x (W/2) pixels per image and
+ * input pixel (hi, wi) reads (hi/2, wi/2) (F.interpolate(scale_factor=2, mode="nearest") folded into the load; H, W even);
+ * geglu_rows = 1: packed row 2i is stored to column i and row 2i + 1 to column i + N/2 (QuantLayer.geglu_rows back in the
+ * reference's column order).  y [B·Ho·Wo][ldy] (y_dtype). */
+int dgq_conv2d_wq(const void* x, int x_dtype, int B, int H, int W, int C, int kh, int kw, int stride, int pad, int upsample,
+                  const uint8_t* w_packed, int w_bits, int Kp, const float* delta, const float* zp, const float* bias, int N,
+                  int geglu_rows, void* y, int y_dtype, int ldy, void* stream);
 
 /* ---- the hot kernel: W4A8 / W8A8 MFMA GEMM with fused dequantisation ------------------------------
  * Replaces F.linear / `w.view(N,-1) @ unfolded` / F.conv2d on fake-quantised operands
