@@ -10,7 +10,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .plan import ActLayout, natural_kperm, round_up, KTILE, act_offset, mark_clears, flush_coefficients
+from .plan import (ActLayout, natural_kperm, natural_ksrc, ksrc_index, ksrc_inverse, round_up, KTILE, act_offset, mark_clears,
+                   flush_coefficients)
 
 _c = ctypes
 
@@ -185,78 +186,39 @@ class PackedWeight:
 class ActBinding:
     """Device-resident tables of one (layer, timestep-slot) activation quantizer."""
 
+    def _table(self, key, make):
+        if key not in self._koff:
+            self._koff[key] = make()
+        return self._koff[key]
+
     def koff(self, W, ldc):
         """ksrc resolved to element offsets (dh*W + dw)*ldc + c for one input geometry (cached)."""
-        if self.ksrc is None:
-            return None
-        key = (W, ldc)
-        if key not in self._koff:
-            e = self.ksrc
-            off = (((e >> 24) & 0x7F) * W + ((e >> 16) & 0xFF)) * ldc + (e & 0xFFFF)
-            self._koff[key] = torch.where(e >= 0, off, torch.full_like(off, -1)).to(torch.int32).contiguous()
-        return self._koff[key]
+        return None if self.ksrc is None else self._table(("off", W, ldc), lambda: ksrc_index(self.ksrc, W, ldc))
 
     def klds(self, kw, C):
         """ksrc resolved to indices (dh*kw + dw)*C + c into the [tap][C] strip a wave stages in LDS (cached)."""
-        if self.ksrc is None:
-            return None
-        key = ("lds", kw, C)
-        if key not in self._koff:
-            e = self.ksrc
-            idx = (((e >> 24) & 0x7F) * kw + ((e >> 16) & 0xFF)) * C + (e & 0xFFFF)
-            self._koff[key] = torch.where(e >= 0, idx, torch.full_like(idx, -1)).to(torch.int32).contiguous()
-        return self._koff[key]
+        return None if self.ksrc is None else self._table(("lds", kw, C), lambda: ksrc_index(self.ksrc, kw, C))
 
     def kdst(self, kw, C, taps):
         """inverse of ksrc: packed position kp of element (tap, c), [taps*C] int32 (cached) — dgq_quant_act's scatter path"""
-        if self.ksrc is None:
-            return None
-        key = ("dst", kw, C, taps)
-        if key not in self._koff:
-            e = self.ksrc
-            valid = e >= 0
-            idx = ((((e >> 24) & 0x7F) * kw + ((e >> 16) & 0xFF)) * C + (e & 0xFFFF))[valid].long()
-            out = torch.full((taps * C,), -1, dtype=torch.int32, device=e.device)
-            out[idx] = torch.nonzero(valid).flatten().to(torch.int32)
-            assert int((out < 0).sum()) == 0, "per-K table does not cover every (tap, channel)"
-            self._koff[key] = out.contiguous()
-        return self._koff[key]
+        return None if self.ksrc is None else self._table(("dst", kw, C, taps), lambda: ksrc_inverse(self.ksrc, kw, C, taps))
 
-    def kpat(self, kh, kw, C, stride):
-        """(dh·PW + dw)·C + c of every packed position inside the input patch of a conv tile (dgq_quant_act's block-staged
-        path; PW from dgq_quant_act_conv_tile), -1 for padding; None when the geometry has no such path.  Cached."""
-        key = ("pat", kh, kw, C, stride)
-        if key not in self._koff:
-            pw_ = _c.c_int(0)
-            tile = _lib.load().dgq_quant_act_conv_tile(C, kh, kw, stride, self.Kp, _c.byref(pw_))
-            if tile == 0:
-                self._koff[key] = None
-            elif self.ksrc is not None:
-                e = self.ksrc
-                idx = (((e >> 24) & 0x7F) * pw_.value + ((e >> 16) & 0xFF)) * C + (e & 0xFFFF)
-                self._koff[key] = torch.where(e >= 0, idx, torch.full_like(idx, -1)).to(torch.int32).contiguous()
-            else:                                                   # natural order kp = tap·C + c, padded to Kp
-                kp = torch.arange(self.Kp, device=self.pw.codes.device)
-                tap, c = kp // C, kp % C
-                idx = ((tap // kw) * pw_.value + (tap % kw)) * C + c
-                self._koff[key] = torch.where(kp < kh * kw * C, idx, torch.full_like(idx, -1)).to(torch.int32).contiguous()
-        return self._koff[key]
+    def conv_patch_width(self, kh, kw, C, stride):
+        """width in pixels of the input patch dgq_quant_act's block-staged path stages for this geometry (dgq_quant_act_conv_tile);
+        0 where the geometry has no such path (cached)"""
+        def ask():
+            pw = _c.c_int(0)
+            return pw.value if _lib.load().dgq_quant_act_conv_tile(C, kh, kw, stride, self.Kp, _c.byref(pw)) else 0
+        return self._table(("patw", kh, kw, C, stride), ask)
 
-    def kpat_for(self, kh, kw, C, pw):
-        """``kpat`` for a patch PW = pw pixels wide (dgq_gemm_act_t.kpat of the conv form of quantise-on-load, csrc/gemm_convq.hip:
-        4 x 8 output positions per workgroup, pw = 8 + kw − 1).  Cached."""
-        key = ("patw", kh, kw, C, pw)
-        if key not in self._koff:
-            if self.ksrc is not None:
-                e = self.ksrc
-                idx = (((e >> 24) & 0x7F) * pw + ((e >> 16) & 0xFF)) * C + (e & 0xFFFF)
-                self._koff[key] = torch.where(e >= 0, idx, torch.full_like(idx, -1)).to(torch.int32).contiguous()
-            else:                                                   # natural order kp = tap·C + c, padded to Kp
-                kp = torch.arange(self.Kp, device=self.pw.codes.device)
-                tap, c = kp // C, kp % C
-                idx = ((tap // kw) * pw + (tap % kw)) * C + c
-                self._koff[key] = torch.where(kp < kh * kw * C, idx, torch.full_like(idx, -1)).to(torch.int32).contiguous()
-        return self._koff[key]
+    def kpat(self, kh, kw, C, pw):
+        """(dh·pw + dw)·C + c of every packed position inside an input patch pw pixels wide, -1 for padding (cached): dgq_quant_act's
+        block-staged path (pw from dgq_quant_act_conv_tile) and dgq_gemm_act_t.kpat of the conv form of quantise-on-load
+        (csrc/gemm_convq.hip: 4 x 8 output positions per workgroup, pw = 8 + kw − 1).  Per-M / scalar layers: the natural order."""
+        def make():
+            e = self.ksrc if self.ksrc is not None else natural_ksrc(C, kh, kw, self.Kp).to(self.pw.codes.device)
+            return ksrc_index(e, pw, C)
+        return self._table(("pat", kh, kw, C, pw), make)
 
     def input_binding(self, C):
         """This (scalar) quantizer applied to the conv's INPUT tensor as a 1x1 layer in natural order: what dgq_quant_act needs to
@@ -442,6 +404,52 @@ def groupnorm_from_partials(gn, groups, eps, gamma, beta):
     return scale, shift
 
 
+def _quant_args(x, geom, ab: ActBinding, pre=None, ln=None, ups=False):
+    """(dgq_quant_act_args_t, the tensors it points to) for the layer input x (channels-last storage) of geometry geom = (B, H, W, C,
+    kh, kw, stride, pad) under ab's tables — with one K split and placeholder outputs: the caller settles the split (quant_splits),
+    allocates and sets ``codes`` / ``rowsum``.  pre / ln / ups as in quant_act."""
+    B, H, W, C, kh, kw, stride, pad = geom
+    per_m = 0 if ab.mode == "perK" else 1
+    ldc = 2 * C if (pre and pre[2] == 2) else C
+    a = _lib.QuantActArgs()
+    a.x, a.x_dtype, a.B, a.H, a.W, a.C, a.kh, a.kw, a.stride, a.pad = x.data_ptr(), _lib.DTYPE_CODE[x.dtype], B, H, W, C, kh, kw, stride, pad
+    a.ksrc, a.koff, a.klds, a.kdst = _dp(ab.ksrc), _dp(ab.koff(W, ldc)), _dp(ab.klds(kw, C)), _dp(ab.kdst(kw, C, kh * kw))
+    if kh * kw > 1 and C % 4 == 0:                           # the block-staged conv path, where the geometry has one
+        pw = ab.conv_patch_width(kh, kw, C, stride)
+        a.kpat = _dp(ab.kpat(kh, kw, C, pw)) if pw else None
+    a.Kp, a.per_m = ab.Kp, per_m
+    a.delta, a.zp = (ab.cdelta.data_ptr(), ab.czp.data_ptr()) if not per_m else (ab.mdelta.data_ptr(), ab.mzp.data_ptr())
+    a.L, a.bits = (1 if not per_m else ab.L), ab.abits
+    keep = [x]
+    if pre and pre[0] is not None:
+        a.pre_scale, a.pre_shift = pre[0].data_ptr(), pre[1].data_ptr()
+        keep += [pre[0], pre[1]]
+    a.pre_act = pre[2] if pre else 0
+    if ln:
+        g, b = as_f32(ln[0]), as_f32(ln[1])
+        a.ln_gamma, a.ln_beta, a.ln_eps = g.data_ptr(), b.data_ptr(), float(ln[2])
+        keep += [g, b]
+    a.ups = 1 if ups else 0
+    a.ksplits = 1
+    a.codes = a.rowsum = 1                                   # placeholders: dgq_quant_act_variant only validates non-NULL
+    return a, keep
+
+
+def quant_splits(a, M):
+    """Settles ``a.ksplits`` of a quantiser problem of M rows and returns it.  The LDS-scatter and block-staged variants (3 / 4 / 5:
+    per-K convs, per-K Linear inputs with short groups, convs whose input patch fits the LDS) take the whole row in one wave / block:
+    they are asked for with one K split first; every other problem is split by act_ksplits.  None where ``a.ups`` is set and the
+    problem takes none of those variants (the folded upsample exists on the scatter / block-staged paths only).  One accepted set
+    serves convolutions and Linear inputs alike: quant_act_variant (csrc/quant_act.hip) answers 5 only with ``kpat`` and more than
+    one tap, and a Linear struct has neither."""
+    a.ksplits = 1
+    if (a.kdst is None and a.kpat is None) or _lib.load().dgq_quant_act_variant(_c.byref(a)) not in (3, 4, 5):
+        if a.ups:
+            return None
+        a.ksplits = act_ksplits(M, a.Kp)
+    return a.ksplits
+
+
 def quant_act(x_cl: torch.Tensor, B, H, W, C, kh, kw, stride, pad, ab: ActBinding, pre=None, ln=None, ups=False):
     """x_cl: contiguous channels-last storage [B][H][W][C] (any fp dtype). Returns (codes, rowsum[parts][M], M).
     pre = (scale [B][C], shift [B][C], act) folds a GroupNorm (+SiLU when act == 1) into the load;
@@ -451,40 +459,19 @@ def quant_act(x_cl: torch.Tensor, B, H, W, C, kh, kw, stride, pad, ab: ActBindin
     Ho = (H + 2 * pad - kh) // stride + 1
     Wo = (W + 2 * pad - kw) // stride + 1
     M = B * Ho * Wo
-    per_m = 0 if ab.mode == "perK" else 1
-    ldc = 2 * C if (pre and pre[2] == 2) else C
-    a = _lib.QuantActArgs()
-    a.x, a.x_dtype, a.B, a.H, a.W, a.C, a.kh, a.kw, a.stride, a.pad = x_cl.data_ptr(), _lib.DTYPE_CODE[x_cl.dtype], B, H, W, C, kh, kw, stride, pad
-    a.ksrc, a.koff, a.klds = _dp(ab.ksrc), _dp(ab.koff(W, ldc)), _dp(ab.klds(kw, C))
-    a.kdst = _dp(ab.kdst(kw, C, kh * kw)) if ab.ksrc is not None else None
-    a.kpat = _dp(ab.kpat(kh, kw, C, stride)) if (kh * kw > 1 and C % 4 == 0) else None
-    a.Kp, a.per_m = ab.Kp, per_m
-    a.delta, a.zp = (ab.cdelta.data_ptr(), ab.czp.data_ptr()) if not per_m else (ab.mdelta.data_ptr(), ab.mzp.data_ptr())
-    a.L, a.bits = (1 if not per_m else ab.L), ab.abits
-    a.pre_scale = _dp(pre[0]) if pre and pre[0] is not None else None
-    a.pre_shift = _dp(pre[1]) if pre and pre[1] is not None else None
-    a.pre_act = pre[2] if pre else 0
-    lnp = (as_f32(ln[0]), as_f32(ln[1]), float(ln[2])) if ln else None
-    a.ln_gamma, a.ln_beta, a.ln_eps = (lnp[0].data_ptr(), lnp[1].data_ptr(), lnp[2]) if lnp else (None, None, 0.0)
-    a.ups = 1 if ups else 0
-    # the LDS-scatter path (per-K convs, per-K Linear inputs with short groups) takes the whole row in one wave / block:
-    # ask for it with one K split first
-    parts = 1
-    a.ksplits = 1
-    a.codes = a.rowsum = 1                                   # placeholders: dgq_quant_act_variant only validates non-NULL
-    if (a.kdst is None and a.kpat is None) or _lib.load().dgq_quant_act_variant(_c.byref(a)) not in (3, 4, 5):
-        if ups:
-            return None                                      # (the folded upsample exists on the scatter / block-staged paths)
-        parts = act_ksplits(M, ab.Kp)
-        a.ksplits = parts
+    a, keep = _quant_args(x_cl, (B, H, W, C, kh, kw, stride, pad), ab, pre, ln, ups)
+    parts = quant_splits(a, M)
+    if parts is None:
+        return None
     codes = torch.empty((M, ab.Kp), dtype=torch.int8, device=x_cl.device)
     rowsum = torch.empty((parts, M), dtype=torch.float32, device=x_cl.device)
     a.codes, a.rowsum = codes.data_ptr(), rowsum.data_ptr()
 
-    def issue():
+    def issue(_keep=keep):
         _lib_call("dgq_quant_act_batch", 1, _c.byref(a), _lib.stream())
     issue()
     if QUANT_LAUNCH_HOOK is not None:
+        ldc = 2 * C if a.pre_act == 2 else C
         QUANT_LAUNCH_HOOK(issue, B * H * W * ldc * x_cl.element_size() >> (2 if ups else 0), M * ab.Kp + 4 * parts * M)
     return codes, rowsum, M
 
@@ -616,7 +603,7 @@ def act_fuses(ab: "ActBinding", M, K, dtype, n_problems=1, x2=None, N=None, Kp=N
 
 
 def _multi_fuses(bindings, M, Kin, dtype, x2):
-    """quant_linear_multi: every shared launch of _quant_linear_multi_fused (one per scale mode and 8 layers) must take quantise-on-load
+    """quant_linear_multi: every shared quantise-on-load launch of _gemm_batches (one per scale mode and 8 layers) must take quantise-on-load
     with the shape the library plans it by — problem 0's N and the launch's widest Kp (dgq_gemm_wxa8_batch)"""
     groups = {}
     for i, ab in enumerate(bindings):
@@ -644,17 +631,29 @@ def conv_act_fuses(ab: "ActBinding", B, H, W, C, kh, kw, stride, pad, dtype, x_s
                                                     0 if ab.mode == "perK" else 1, dt, dt))
 
 
-def make_act(x2: torch.Tensor, ab: "ActBinding", pre=None, ln=None, rows_per_image=1):
+def make_act(x2: torch.Tensor, ab: "ActBinding", pre=None, ln=None, rows_per_image=1, conv=None):
     """dgq_gemm_act_t for the rows x2 [M][K] (row stride = stride(0)) under the layer's activation quantizer; pre = (scale, shift,
-    act) a folded GroupNorm (+ SiLU), ln = (gamma, beta, eps) a folded LayerNorm.  Keeps its tensors alive on the struct."""
-    K = ab.pw.K
+    act) a folded GroupNorm (+ SiLU), ln = (gamma, beta, eps) a folded LayerNorm.  conv = (B, H, W, C, kh, kw, stride, pad): the conv
+    form (csrc/gemm_convq.hip) — x2 is the contiguous [B][H][W][C] storage and the launch stages input patches of it.  Keeps its
+    tensors alive on the struct."""
     a = _lib.GemmAct()
-    a.x, a.x_dtype, a.ldx, a.K = x2.data_ptr(), _lib.DTYPE_CODE[x2.dtype], x2.stride(0), K
+    a.x, a.x_dtype = x2.data_ptr(), _lib.DTYPE_CODE[x2.dtype]
     keep = [x2]
+    if conv is None:
+        a.ldx, a.K = x2.stride(0), ab.pw.K
+        if ab.mode == "perK":
+            kd = ab.kdst(1, ab.pw.K, 1)
+            a.kdst = kd.data_ptr()
+            keep.append(kd)
+    else:
+        B, H, W, C, kh, kw, stride, pad = conv
+        kp = ab.kpat(kh, kw, C, 8 + kw - 1)
+        a.ldx = a.K = C
+        a.kpat = kp.data_ptr()
+        a.B, a.H, a.W, a.kh, a.kw, a.stride, a.pad = B, H, W, kh, kw, stride, pad
+        keep.append(kp)
     if ab.mode == "perK":
-        kd = ab.kdst(1, K, 1)
-        a.kdst, a.czp = kd.data_ptr(), ab.czp.data_ptr()
-        keep.append(kd)
+        a.czp = ab.czp.data_ptr()
     a.bits = ab.abits
     a.rows_per_image, a.pre_act = rows_per_image, 0
     if pre is not None:
@@ -670,33 +669,61 @@ def make_act(x2: torch.Tensor, ab: "ActBinding", pre=None, ln=None, rows_per_ima
     return a
 
 
-def gemm_act(x2, M, ab: "ActBinding", out_dtype, extra=None, pre=None, ln=None, rows_per_image=1, out=None):
-    """one launch: aqtizer(x2) @ Wᵀ with the layer's epilogue — dgq_gemm_wxa8 with quantise-on-load (see act_fuses)"""
-    act = make_act(x2, ab, pre, ln, rows_per_image)
+def _with_act(extra, ab: "ActBinding", M, act):
+    """extra (see with_layer_tables) carrying the quantise-on-load descriptor ``act``"""
     extra = with_layer_tables(extra, ab, M)
     extra.act = _c.cast(_c.pointer(act), _c.c_void_p)
     extra._act_keep = act
-    dummy = ab.wfrag                                          # codes / rowsum are ignored under quantise-on-load: any device pointer
-    return gemm_wxa8(dummy, dummy, M, ab, out_dtype, out=out, extra=extra, _fused_bytes=x2.element_size() * M * ab.pw.K)
+    return extra
+
+
+def gemm_act(x2, M, ab: "ActBinding", out_dtype, extra=None, pre=None, ln=None, rows_per_image=1, out=None):
+    """one launch: aqtizer(x2) @ Wᵀ with the layer's epilogue — dgq_gemm_wxa8 with quantise-on-load (see act_fuses)"""
+    extra = _with_act(extra, ab, M, make_act(x2, ab, pre, ln, rows_per_image))
+    return gemm_wxa8(None, None, M, ab, out_dtype, out=out, extra=extra, _fused_bytes=x2.element_size() * M * ab.pw.K)
+
+
+def _gemm_args(ab: ActBinding, M, codes, rowsum, parts, out, extra):
+    """dgq_gemm_args_t of one layer: codes [M][Kp] and rowsum [parts][M] as a dgq_quant_act launch wrote them — or None for both
+    where extra.act makes the launch quantise its own operand: both are ignored then and only have to be device pointers, with
+    one row-sum part.  The scale tables follow the layer's mode: cdelta / cflush per-K, mdelta / mzp / vn and L per-M and scalar."""
+    pw = ab.pw
+    per_m = 0 if ab.mode == "perK" else 1
+    g = _lib.GemmArgs()
+    if codes is None:
+        g.codes = g.rowsum = ab.wfrag.data_ptr()
+        g.rowsum_parts = 1
+    else:
+        g.codes, g.rowsum, g.rowsum_parts = codes.data_ptr(), rowsum.data_ptr(), parts
+    g.M, g.Kp, g.wpacked, g.w_bits, g.N, g.per_m = M, ab.Kp, ab.wpacked.data_ptr(), pw.bits, pw.N, per_m
+    if per_m:
+        g.mdelta, g.mzp, g.L, g.vn = ab.mdelta.data_ptr(), ab.mzp.data_ptr(), ab.L, ab.vn.data_ptr()
+    else:
+        g.cdelta, g.cflush, g.L = ab.cdelta.data_ptr(), ab.cflush.data_ptr(), 1
+    g.offset = ab.offset
+    g.alpha, g.zw, g.gamma = pw.alpha.data_ptr(), pw.zw.data_ptr(), ab.gamma.data_ptr()
+    g.y, g.y_dtype, g.ldy = out.data_ptr(), _lib.DTYPE_CODE[out.dtype], out.stride(0)
+    if extra is not None:
+        g.extra = _c.cast(_c.pointer(extra), _c.c_void_p)
+        g._extra_keep = extra
+    return g
 
 
 def gemm_wxa8(codes, rowsum, M, ab: ActBinding, out_dtype, out: Optional[torch.Tensor] = None, extra=None, _fused_bytes=0):
-    pw = ab.pw
-    ws = workspace(codes.device)
+    """One dgq_gemm_wxa8 launch (split-K, the implicit-conv tiles and the conv-quantiser kernel are this entry's alone).  codes =
+    rowsum = None where extra.act makes the launch quantise its own operand.  _fused_bytes: the fp input such a launch reads, for
+    GEMM_LAUNCH_HOOK only."""
+    assert codes is not None or (extra is not None and extra.act), "dgq gemm_wxa8: no code matrix and no quantise-on-load descriptor"
+    dev = ab.wpacked.device
+    ws = workspace(dev)
     extra = with_layer_tables(extra, ab, M)
     if out is None:
-        out = torch.empty((M, pw.N // 2 if (extra is not None and extra.geglu) else pw.N), dtype=out_dtype, device=codes.device)
-    per_m = 0 if ab.mode == "perK" else 1
-    parts = rowsum.shape[0] if (rowsum.dim() == 2 and not _fused_bytes) else 1
-    def issue():
-        _lib_call("dgq_gemm_wxa8", _lib.ptr(codes), _lib.ptr(rowsum), parts, M, ab.Kp, _lib.ptr(ab.wpacked), pw.bits, pw.N,
-                  per_m,
-                  _lib.ptr(ab.cdelta) if not per_m else None, _lib.ptr(ab.cflush) if not per_m else None,
-                  _lib.ptr(ab.mdelta) if per_m else None, _lib.ptr(ab.mzp) if per_m else None,
-                  ab.L if per_m else 1, _c.c_float(ab.offset),
-                  _lib.ptr(pw.alpha), _lib.ptr(pw.zw), _lib.ptr(ab.gamma), _lib.ptr(ab.vn) if per_m else None,
-                  _lib.ptr(out), _lib.DTYPE_CODE[out.dtype], out.stride(0), _lib.ptr(ws), ws.numel(),
-                  _c.byref(extra) if extra is not None else None, _lib.stream())
+        out = torch.empty((M, ab.pw.N // 2 if (extra is not None and extra.geglu) else ab.pw.N), dtype=out_dtype, device=dev)
+    g = _gemm_args(ab, M, codes, rowsum, rowsum.shape[0] if (rowsum is not None and rowsum.dim() == 2) else 1, out, None)
+    head = [getattr(g, name) for name, _ in _lib.GemmArgs._fields_[:22]]      # (the entry's first 22 parameters, in its order)
+
+    def issue(_keep=(codes, rowsum, out, g, ab)):
+        _lib_call("dgq_gemm_wxa8", *head, _lib.ptr(ws), ws.numel(), _c.byref(extra) if extra is not None else None, _lib.stream())
     issue()
     if GEMM_LAUNCH_HOOK is not None:
         GEMM_LAUNCH_HOOK(issue, [(M, ab, out.element_size(), _fused_bytes)])
@@ -727,126 +754,100 @@ def quant_linear(x: torch.Tensor, ab: ActBinding, pre_act=0, residual=None, fq=N
     return y.view(*x.shape[:-1], y.shape[-1])
 
 
-def _quant_linear_multi_fused(x, x2, M, bindings, ln):
-    """quant_linear_multi as dgq_gemm_wxa8_batch launches with quantise-on-load: one launch per scale mode and 8 layers"""
-    dev = x2.device
-    outs = [torch.empty((M, ab.pw.N), dtype=x.dtype, device=dev) for ab in bindings]
+def _gemm_batches(bindings, M, outs, key, problem):
+    """The dgq_gemm_wxa8_batch launches of a quant_linear_multi call: the layers grouped by key(i), 8 problems per launch;
+    problem(i, j) -> (codes, rowsum, parts, extra, input_bytes) of layer i as problem j of its launch (see _gemm_args and
+    GEMM_LAUNCH_HOOK)."""
     groups = {}
-    for i, ab in enumerate(bindings):
-        groups.setdefault(0 if ab.mode == "perK" else 1, []).append(i)
-    for per_m, idxs in groups.items():
+    for i in range(len(bindings)):
+        groups.setdefault(key(i), []).append(i)
+    for idxs in groups.values():
         for j0 in range(0, len(idxs), 8):
             chunk = idxs[j0:j0 + 8]
-            arr = (_lib.GemmArgs * len(chunk))()
-            extras = []
-            for g, i in zip(arr, chunk):
-                ab, pw = bindings[i], bindings[i].pw
-                act = make_act(x2, ab, None, ln)
-                ex = with_layer_tables(None, ab, 0)
-                ex.act = _c.cast(_c.pointer(act), _c.c_void_p)
-                extras.append((ex, act))
-                g.codes, g.rowsum, g.rowsum_parts, g.M, g.Kp = ab.wfrag.data_ptr(), ab.wfrag.data_ptr(), 1, M, ab.Kp
-                g.wpacked, g.w_bits, g.N, g.per_m = ab.wpacked.data_ptr(), pw.bits, pw.N, per_m
-                g.cdelta, g.cflush = (ab.cdelta.data_ptr(), ab.cflush.data_ptr()) if not per_m else (None, None)
-                g.mdelta, g.mzp = (ab.mdelta.data_ptr(), ab.mzp.data_ptr()) if per_m else (None, None)
-                g.L, g.offset = (ab.L if per_m else 1), ab.offset
-                g.alpha, g.zw, g.gamma, g.vn = pw.alpha.data_ptr(), pw.zw.data_ptr(), ab.gamma.data_ptr(), (ab.vn.data_ptr() if per_m else None)
-                g.y, g.y_dtype, g.ldy = outs[i].data_ptr(), _lib.DTYPE_CODE[outs[i].dtype], outs[i].stride(0)
-                g.extra = _c.cast(_c.pointer(ex), _c.c_void_p)
-            n_chunk = len(chunk)
+            probs = [problem(i, j) for j, i in enumerate(chunk)]
+            gs = [_gemm_args(bindings[i], M, p[0], p[1], p[2], outs[i], p[3]) for i, p in zip(chunk, probs)]
+            arr = (_lib.GemmArgs * len(gs))(*gs)
 
-            def issue(arr=arr, n_chunk=n_chunk, _keep=extras):
+            def issue(arr=arr, n_chunk=len(gs), _keep=gs):
                 _lib_call("dgq_gemm_wxa8_batch", n_chunk, _c.cast(arr, _c.c_void_p), _lib.stream())
             issue()
             if GEMM_LAUNCH_HOOK is not None:
-                GEMM_LAUNCH_HOOK(issue, [(M, bindings[i], outs[i].element_size(), (M * bindings[i].pw.K * x2.element_size()) if j == 0 else 0)
-                                         for j, i in enumerate(chunk)])      # (one shared input: counted once)
-    return [o.view(*x.shape[:-1], o.shape[-1]) for o in outs]
+                GEMM_LAUNCH_HOOK(issue, [(M, bindings[i], outs[i].element_size(), p[4]) for i, p in zip(chunk, probs)])
 
 
 def quant_linear_multi(x: torch.Tensor, bindings, ln=None):
     """[quant_linear(x, ab, ln=ln) for ab in bindings] with the launches shared: layers that consume the SAME input — the
     q / k / v projections of a self-attention, the to_k / to_v of every cross-attention (one text context) — are quantised
     by one dgq_quant_act_batch per (kernel variant, scale mode) and multiplied by one dgq_gemm_wxa8_batch per scale mode,
-    8 problems per launch.  Same kernels, same arithmetic, same results as the one-layer calls."""
+    8 problems per launch — or, where every such launch may quantise its own rows (_multi_fuses), by the latter alone.  Same
+    kernels, same arithmetic, same results as the one-layer calls."""
     Kin = x.shape[-1]
     x2 = x.reshape(-1, Kin)
     if not x2.is_contiguous():
         x2 = x2.contiguous()
     M = x2.shape[0]
     dev = x2.device
-    lib = _lib.load()
+    outs = [torch.empty((M, ab.pw.N), dtype=x.dtype, device=dev) for ab in bindings]
+    per_m = [0 if ab.mode == "perK" else 1 for ab in bindings]
     if _multi_fuses(bindings, M, Kin, x.dtype, x2):
-        return _quant_linear_multi_fused(x, x2, M, bindings, ln)
-    lnp = (as_f32(ln[0]), as_f32(ln[1]), float(ln[2])) if ln else None
-    qa, keep = [], []
+        def fused(i, j):                               # (one shared input: its bytes are counted on the launch's first problem)
+            ab = bindings[i]
+            return None, None, 1, _with_act(None, ab, 0, make_act(x2, ab, None, ln)), (M * Kin * x2.element_size() if j == 0 else 0)
+        _gemm_batches(bindings, M, outs, lambda i: per_m[i], fused)
+        return [o.view(*x.shape[:-1], o.shape[-1]) for o in outs]
+    lib = _lib.load()
+    qa = []
     for ab in bindings:
         assert ab.pw.K == Kin and ab.pw.taps == 1
-        per_m = 0 if ab.mode == "perK" else 1
-        a = _lib.QuantActArgs()
-        a.x, a.x_dtype, a.B, a.H, a.W, a.C, a.kh, a.kw, a.stride, a.pad = x2.data_ptr(), _lib.DTYPE_CODE[x2.dtype], M, 1, 1, Kin, 1, 1, 1, 0
-        a.ksrc, a.koff, a.klds = _dp(ab.ksrc), _dp(ab.koff(1, Kin)), _dp(ab.klds(1, Kin))
-        a.kdst = _dp(ab.kdst(1, Kin, 1)) if ab.ksrc is not None else None
-        a.Kp, a.per_m = ab.Kp, per_m
-        a.delta, a.zp = (ab.cdelta.data_ptr(), ab.czp.data_ptr()) if not per_m else (ab.mdelta.data_ptr(), ab.mzp.data_ptr())
-        a.L, a.bits = (1 if not per_m else ab.L), ab.abits
-        a.pre_scale = a.pre_shift = None
-        a.pre_act = 0
-        a.ln_gamma, a.ln_beta, a.ln_eps = (lnp[0].data_ptr(), lnp[1].data_ptr(), lnp[2]) if lnp else (None, None, 0.0)
-        a.codes = a.rowsum = 1                               # placeholders: dgq_quant_act_variant only validates non-NULL
-        parts, a.ksplits = 1, 1                              # the scatter path takes whole rows: ask for it unsplit first
-        if a.kdst is None or lib.dgq_quant_act_variant(_c.byref(a)) not in (3, 4):
-            parts = act_ksplits(M, ab.Kp)
-            a.ksplits = parts
+        a, keep = _quant_args(x2, (M, 1, 1, Kin, 1, 1, 1, 0), ab, None, ln)
+        parts = quant_splits(a, M)
         codes = torch.empty((M, ab.Kp), dtype=torch.int8, device=dev)
         rowsum = torch.empty((parts, M), dtype=torch.float32, device=dev)
         a.codes, a.rowsum = codes.data_ptr(), rowsum.data_ptr()
-        variant = lib.dgq_quant_act_variant(_c.byref(a))
-        qa.append((variant, per_m, a, codes, rowsum, parts))
+        qa.append((lib.dgq_quant_act_variant(_c.byref(a)), a, codes, rowsum, parts, keep))
     groups = {}
-    for i, (variant, per_m, a, *_rest) in enumerate(qa):
-        groups.setdefault((variant, per_m), []).append(i)
+    for i, q in enumerate(qa):
+        groups.setdefault((q[0], per_m[i]), []).append(i)
     for idxs in groups.values():
         for j0 in range(0, len(idxs), 8):
             chunk = idxs[j0:j0 + 8]
-            arr = (_lib.QuantActArgs * len(chunk))(*[qa[i][2] for i in chunk])
+            arr = (_lib.QuantActArgs * len(chunk))(*[qa[i][1] for i in chunk])
 
-            def issue_q(arr=arr, n_chunk=len(chunk)):
+            def issue_q(arr=arr, n_chunk=len(chunk), _keep=[qa[i] for i in chunk]):
                 _lib_call("dgq_quant_act_batch", n_chunk, _c.cast(arr, _c.c_void_p), _lib.stream())
             issue_q()
             if QUANT_LAUNCH_HOOK is not None:          # one shared input, one code matrix + row sums per problem
-                QUANT_LAUNCH_HOOK(issue_q, M * Kin * x2.element_size(), sum(M * bindings[i].Kp + 4 * qa[i][5] * M for i in chunk))
-    outs = [torch.empty((M, ab.pw.N), dtype=x.dtype, device=dev) for ab in bindings]
-    ggroups = {}
-    for i, ab in enumerate(bindings):
-        ggroups.setdefault((qa[i][1], ab.pw.bits), []).append(i)
-    for (per_m, _bits), idxs in ggroups.items():
-        for j0 in range(0, len(idxs), 8):
-            chunk = idxs[j0:j0 + 8]
-            arr = (_lib.GemmArgs * len(chunk))()
-            extras = []
-            for g, i in zip(arr, chunk):
-                ab, pw = bindings[i], bindings[i].pw
-                _v, _pm, _a, codes, rowsum, parts = qa[i]
-                g.codes, g.rowsum, g.rowsum_parts, g.M, g.Kp = codes.data_ptr(), rowsum.data_ptr(), parts, M, ab.Kp
-                g.wpacked, g.w_bits, g.N, g.per_m = ab.wpacked.data_ptr(), pw.bits, pw.N, per_m
-                g.cdelta, g.cflush = (ab.cdelta.data_ptr(), ab.cflush.data_ptr()) if not per_m else (None, None)
-                g.mdelta, g.mzp = (ab.mdelta.data_ptr(), ab.mzp.data_ptr()) if per_m else (None, None)
-                g.L, g.offset = (ab.L if per_m else 1), ab.offset
-                g.alpha, g.zw, g.gamma, g.vn = pw.alpha.data_ptr(), pw.zw.data_ptr(), ab.gamma.data_ptr(), (ab.vn.data_ptr() if per_m else None)
-                ex = with_layer_tables(None, ab, 0)
-                extras.append(ex)
-                g.y, g.y_dtype, g.ldy = outs[i].data_ptr(), _lib.DTYPE_CODE[outs[i].dtype], outs[i].stride(0)
-                g.extra = _c.cast(_c.pointer(ex), _c.c_void_p) if ex is not None else None
-            n_chunk = len(chunk)
-
-            def issue(arr=arr, n_chunk=n_chunk, _keep=extras):
-                _lib_call("dgq_gemm_wxa8_batch", n_chunk, _c.cast(arr, _c.c_void_p), _lib.stream())
-            issue()
-            if GEMM_LAUNCH_HOOK is not None:
-                GEMM_LAUNCH_HOOK(issue, [(M, bindings[i], outs[i].element_size(), 0) for i in chunk])
-    keep.append(qa)
+                QUANT_LAUNCH_HOOK(issue_q, M * Kin * x2.element_size(), sum(M * bindings[i].Kp + 4 * qa[i][4] * M for i in chunk))
+    _gemm_batches(bindings, M, outs, lambda i: (per_m[i], bindings[i].pw.bits),
+                  lambda i, j: (qa[i][2], qa[i][3], qa[i][4], with_layer_tables(None, bindings[i], 0), 0))
     return [o.view(*x.shape[:-1], o.shape[-1]) for o in outs]
+
+
+def _gn_input(x, x_store, norm):
+    """(scale, shift) [B][C] of the GroupNorm norm = (groups, eps, gamma, beta, act) of x (logical NCHW; x_store its [B][H][W][C]
+    storage): from the partials the producing GEMM(s) left on x, else by a statistics pass"""
+    groups, eps, gamma, beta, _act = norm
+    B, C, H, W = x.shape
+    gn = _gn_of(x)
+    if gn is not None and gn["B"] == B and gn["HW"] == H * W and gn["C"] == C and C % groups == 0:
+        return groupnorm_from_partials(gn, groups, eps, gamma, beta)
+    return groupnorm_scale_shift(x_store, B, H * W, C, groups, eps, gamma, beta)
+
+
+def _gn_partial(want, M, N, HW, device):
+    """the [M/16][N][2] buffer a launch writes the GroupNorm partials of its [M][N] output (HW rows per image) into, for whoever
+    normalises it next — where the caller wants them (its own condition) and the epilogues can form them; else None"""
+    if want and GN_FROM_GEMM and HW % 16 == 0 and N % 4 == 0:
+        return torch.empty((M // 16, N, 2), dtype=torch.float32, device=device)
+    return None
+
+
+def _gn_tagged(y, part, B, Ho, Wo, N):
+    """the [M][N] rows y as the logical NCHW output, carrying its GroupNorm partials (if any) as ``_dgq_gn``"""
+    out = y.view(B, Ho, Wo, N).permute(0, 3, 1, 2)
+    if part is not None:
+        out._dgq_gn = dict(parts=[(part, N)], B=B, HW=Ho * Wo, C=N, ver=out._version)
+    return out
 
 
 def quant_conv2d(x: torch.Tensor, ab: ActBinding, kh, kw, stride, pad, norm=None, residual=None, bias_rows=None, gn_out=True, upsample=False,
@@ -866,58 +867,32 @@ def quant_conv2d(x: torch.Tensor, ab: ActBinding, kh, kw, stride, pad, norm=None
         H, W = 2 * H, 2 * W                           # the layer's input geometry; x stays the (H/2) x (W/2) source
     xc = x.contiguous(memory_format=torch.channels_last)
     x_store = xc.permute(0, 2, 3, 1)                  # [B,H,W,C] view over the same storage, contiguous
-    pre = None
-    if norm is not None:
-        groups, eps, gamma, beta, act = norm
-        gn = _gn_of(x)
-        if gn is not None and gn["B"] == B and gn["HW"] == H * W and gn["C"] == C and C % groups == 0:
-            sc, sh = groupnorm_from_partials(gn, groups, eps, gamma, beta)      # statistics left by the producing GEMM(s)
-        else:
-            sc, sh = groupnorm_scale_shift(x_store, B, H * W, C, groups, eps, gamma, beta)
-        pre = (sc, sh, act)
+    pre = (*_gn_input(x, x_store, norm), norm[4]) if norm is not None else None
     Ho = (H + 2 * pad - kh) // stride + 1
     Wo = (W + 2 * pad - kw) // stride + 1
     M = B * Ho * Wo
+    N = ab.pw.N
     res2, res_div = None, 1
     if residual is not None:
-        res2 = residual.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1).reshape(M, ab.pw.N)
+        res2 = residual.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1).reshape(M, N)
     elif bias_rows is not None:                       # [B][N]: one row per image, broadcast over its Ho*Wo positions
         res2, res_div = bias_rows.contiguous(), M // B
-    N = ab.pw.N
+
+    def extra_with(part, conv=None):
+        return make_extra(res2, res_div=res_div, gn_partial=part, conv=conv, y2=out2)
     if kh == 1 and kw == 1 and stride == 1 and pad == 0 and act_fuses(ab, M, C, x.dtype, x2=x_store.reshape(M, C)):
         # a 1x1 convolution is a Linear layer over the pixels: one launch, the GEMM quantises its own rows (dgq_gemm_act_t)
-        part = torch.empty((M // 16, N, 2), dtype=torch.float32, device=x.device) if (GN_FROM_GEMM and gn_out and (Ho * Wo) % 16 == 0 and N % 4 == 0) else None
-        y = gemm_act(x_store.reshape(M, C), M, ab, x.dtype, extra=make_extra(res2, res_div=res_div, gn_partial=part, y2=out2), pre=pre, rows_per_image=H * W,
-                     out=out)
-        out = y.view(B, Ho, Wo, N).permute(0, 3, 1, 2)
-        if part is not None:
-            out._dgq_gn = dict(parts=[(part, N)], B=B, HW=Ho * Wo, C=N, ver=out._version)
-        return out
+        part = _gn_partial(gn_out, M, N, Ho * Wo, x.device)
+        y = gemm_act(x_store.reshape(M, C), M, ab, x.dtype, extra=extra_with(part), pre=pre, rows_per_image=H * W, out=out)
+        return _gn_tagged(y, part, B, Ho, Wo, N)
     if kh * kw > 1 and not upsample and conv_act_fuses(ab, B, H, W, C, kh, kw, stride, pad, x.dtype, x_store):
         # the unfolded operand is quantised INSIDE the GEMM launch from a staged input patch (dgq_gemm_act_t with kh > 1): one launch,
         # no code matrix (QuantLayer.forward, quant_layer.py:626-661, as one kernel)
-        part = torch.empty((M // 16, N, 2), dtype=torch.float32, device=x.device) if (GN_FROM_GEMM and gn_out and (Ho * Wo) % 16 == 0 and N % 4 == 0) else None
-        act = _lib.GemmAct()
-        kp_ = ab.kpat_for(kh, kw, C, 8 + kw - 1)
-        act.x, act.x_dtype, act.ldx, act.K = x_store.data_ptr(), _lib.DTYPE_CODE[x_store.dtype], C, C
-        act.kpat, act.bits, act.rows_per_image, act.pre_act = kp_.data_ptr(), ab.abits, H * W, 0
-        act.B, act.H, act.W, act.kh, act.kw, act.stride, act.pad = B, H, W, kh, kw, stride, pad
-        act._keep = [x_store, kp_]
-        if ab.mode == "perK":
-            act.czp = ab.czp.data_ptr()
-        if pre is not None:
-            if pre[0] is not None:
-                act.pre_scale, act.pre_shift = pre[0].data_ptr(), pre[1].data_ptr()
-                act._keep += [pre[0], pre[1]]
-            act.pre_act = pre[2]
-        extra = with_layer_tables(make_extra(res2, res_div=res_div, gn_partial=part, y2=out2), ab, M)
-        extra.act = _c.cast(_c.pointer(act), _c.c_void_p)
-        extra._act_keep = act
-        y = gemm_wxa8(ab.wfrag, ab.wfrag, M, ab, x.dtype, out=out, extra=extra, _fused_bytes=x.element_size() * B * H * W * C)
-        out = y.view(B, Ho, Wo, N).permute(0, 3, 1, 2)
-        if part is not None:
-            out._dgq_gn = dict(parts=[(part, N)], B=B, HW=Ho * Wo, C=N, ver=out._version)
-        return out
+        part = _gn_partial(gn_out, M, N, Ho * Wo, x.device)
+        act = make_act(x_store, ab, pre, rows_per_image=H * W, conv=(B, H, W, C, kh, kw, stride, pad))
+        y = gemm_wxa8(None, None, M, ab, x.dtype, out=out, extra=_with_act(extra_with(part), ab, M, act),
+                      _fused_bytes=x.element_size() * B * H * W * C)
+        return _gn_tagged(y, part, B, Ho, Wo, N)
     implicit = CONV_IMPLICIT and ab.mode == "scalar" and kh * kw > 1 and C % 16 == 0 and ab.pw.bits == 4 and ab.conv_zero_code() is not None
     conv_desc = None
     if implicit:
@@ -938,18 +913,31 @@ def quant_conv2d(x: torch.Tensor, ab: ActBinding, kh, kw, stride, pad, norm=None
             return quant_conv2d(F.interpolate(x, scale_factor=2.0, mode="nearest"), ab, kh, kw, stride, pad, norm=norm, residual=residual,
                                 bias_rows=bias_rows, gn_out=gn_out, out=out, out2=out2)
         codes, rowsum, M = qa
-    # GroupNorm partials of the output for whoever normalises it next: from the GEMM's own epilogue, or — a K-split launch —
-    # from its combine kernel (DGQ_GN_FROM_SPLITK=0: only unsplit launches, the tensor gets a statistics pass otherwise)
-    N = ab.pw.N
-    part = None
-    if (GN_FROM_GEMM and gn_out and (Ho * Wo) % 16 == 0 and N % 4 == 0 and
-            (GN_FROM_SPLITK or _lib.load().dgq_gemm_plan_splits(M, N, ab.Kp, ab.pw.bits, 0 if ab.mode == "perK" else 1, WORKSPACE_BYTES) == 1)):
-        part = torch.empty((M // 16, N, 2), dtype=torch.float32, device=x.device)
-    y = gemm_wxa8(codes, rowsum, M, ab, x.dtype, out=out, extra=make_extra(res2, res_div=res_div, gn_partial=part, conv=conv_desc, y2=out2))
-    out = y.view(B, Ho, Wo, N).permute(0, 3, 1, 2)
-    if part is not None:
-        out._dgq_gn = dict(parts=[(part, N)], B=B, HW=Ho * Wo, C=N, ver=out._version)
-    return out
+    # GroupNorm partials of the output: from the GEMM's own epilogue, or — a K-split launch — from its combine kernel
+    # (DGQ_GN_FROM_SPLITK=0: only unsplit launches, the tensor gets a statistics pass otherwise)
+    part = _gn_partial(gn_out and (GN_FROM_SPLITK or _lib.load().dgq_gemm_plan_splits(M, N, ab.Kp, ab.pw.bits, 0 if ab.mode == "perK" else 1,
+                                                                                      WORKSPACE_BYTES) == 1), M, N, Ho * Wo, x.device)
+    y = gemm_wxa8(codes, rowsum, M, ab, x.dtype, out=out, extra=extra_with(part, conv_desc))
+    return _gn_tagged(y, part, B, Ho, Wo, N)
+
+
+def _weight_only_operand(x, K, kh, kw, stride, pad, upsample, what):
+    """What the weight-only kernels read of x for a weight of K columns: (storage, (B, H, W, C, kh, kw, stride, pad), rows -> result).
+    x logical NCHW with K = kh·kw·C (made channels-last; ``upsample``: seen through a 2x nearest upsample), or [..., K] for a
+    Linear layer (kh = kw = 1, any rank: the rows are everything but the last dimension)."""
+    if x.dim() == 4 and K == kh * kw * x.shape[1]:
+        B, C, H, W = x.shape
+        if upsample:
+            H, W = 2 * H, 2 * W
+        Ho = (H + 2 * pad - kh) // stride + 1
+        Wo = (W + 2 * pad - kw) // stride + 1
+        return (x.contiguous(memory_format=torch.channels_last), (B, H, W, C, kh, kw, stride, pad),
+                lambda y: y.view(B, Ho, Wo, -1).permute(0, 3, 1, 2))
+    assert K == x.shape[-1] and kh == kw == 1 and not upsample, "dgq %s: weight [N][%d] does not match input %s" % (what, K, tuple(x.shape))
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    return x2, (x2.shape[0], 1, 1, K, 1, 1, 1, 0), lambda y: y.view(*x.shape[:-1], -1)
 
 
 def conv2d_f32w(x: torch.Tensor, w_nat: torch.Tensor, bias, kh, kw, stride, pad, norm=None, out2=None, gn_out=False):
@@ -958,45 +946,23 @@ def conv2d_f32w(x: torch.Tensor, w_nat: torch.Tensor, bias, kh, kw, stride, pad,
     (kh = kw = 1); w_nat [N][kh·kw·C] fp32 with K in (tap, c) order; bias [N] fp32 or None.
     norm = (groups, eps, gamma, beta, act) folds GroupNorm (+SiLU) of a 4-D x into the load, as in quant_conv2d."""
     N = w_nat.shape[0]
-    is_conv = x.dim() == 4 and w_nat.shape[1] == kh * kw * x.shape[1]
-    if x.dim() == 4 and not is_conv:
-        # a Linear layer fed a 4-D [..., K] input (F.linear takes any rank): the rows are everything but the last dimension
-        assert kh == kw == 1 and w_nat.shape[1] == x.shape[-1], "dgq conv2d_f32w: weight [N][%d] does not match input %s" % (w_nat.shape[1], tuple(x.shape))
-    if is_conv:
-        B, C, H, W = x.shape
-        xs = x.contiguous(memory_format=torch.channels_last)
-        sc = sh = None
-        act = 0
-        if norm is not None:
-            groups, eps, gamma, beta, act = norm
-            gn = _gn_of(x)
-            if gn is not None and gn["B"] == B and gn["HW"] == H * W and gn["C"] == C and C % groups == 0:
-                sc, sh = groupnorm_from_partials(gn, groups, eps, gamma, beta)
-            else:
-                sc, sh = groupnorm_scale_shift(xs.permute(0, 2, 3, 1), B, H * W, C, groups, eps, gamma, beta)
-        Ho = (H + 2 * pad - kh) // stride + 1
-        Wo = (W + 2 * pad - kw) // stride + 1
-        y = torch.empty((B * Ho * Wo, N), dtype=x.dtype, device=x.device)
-        part = None
-        if gn_out and GN_FROM_GEMM and (Ho * Wo) % 16 == 0 and N % 4 == 0 and N > 8:      # statistics for whoever normalises the output next
-            part = torch.empty((B * Ho * Wo // 16, N, 2), dtype=torch.float32, device=x.device)
-        _lib_call("dgq_conv2d_f32w", _lib.ptr(xs), _lib.DTYPE_CODE[x.dtype], B, H, W, C, kh, kw, stride, pad,
-                  _lib.ptr(w_nat), _lib.ptr(bias), N, _lib.ptr(y), _lib.DTYPE_CODE[y.dtype], N,
-                  _lib.ptr(sc), _lib.ptr(sh), int(act), _lib.ptr(out2), out2.stride(0) if out2 is not None else 0, _lib.ptr(part), _lib.stream())
-        out = y.view(B, Ho, Wo, N).permute(0, 3, 1, 2)
-        if part is not None:
-            out._dgq_gn = dict(parts=[(part, N)], B=B, HW=Ho * Wo, C=N, ver=out._version)
-        return out
-    K = x.shape[-1]
-    assert w_nat.shape[1] == K and kh == kw == 1, "dgq conv2d_f32w: weight [N][%d] does not match input %s" % (w_nat.shape[1], tuple(x.shape))
-    x2 = x.reshape(-1, K)
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
-    y = torch.empty((x2.shape[0], N), dtype=x.dtype, device=x.device)
-    assert norm is None
-    _lib_call("dgq_conv2d_f32w", _lib.ptr(x2), _lib.DTYPE_CODE[x.dtype], x2.shape[0], 1, 1, K, 1, 1, 1, 0,
-              _lib.ptr(w_nat), _lib.ptr(bias), N, _lib.ptr(y), _lib.DTYPE_CODE[y.dtype], N, None, None, 0, None, 0, None, _lib.stream())
-    return y.view(*x.shape[:-1], N)
+    xs, geom, result = _weight_only_operand(x, w_nat.shape[1], kh, kw, stride, pad, False, "conv2d_f32w")
+    is_conv = xs.dim() == 4
+    assert is_conv or norm is None
+    if not is_conv:
+        out2 = None                                     # (a Linear call has never honoured it)
+    sc, sh = _gn_input(x, xs.permute(0, 2, 3, 1), norm) if norm is not None else (None, None)
+    B, H, W = geom[:3]
+    Ho = (H + 2 * pad - kh) // stride + 1
+    Wo = (W + 2 * pad - kw) // stride + 1
+    M = B * Ho * Wo
+    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    part = _gn_partial(gn_out and is_conv and N > 8, M, N, Ho * Wo, x.device)
+    _lib_call("dgq_conv2d_f32w", _lib.ptr(xs), _lib.DTYPE_CODE[x.dtype], *geom,
+              _lib.ptr(w_nat), _lib.ptr(bias), N, _lib.ptr(y), _lib.DTYPE_CODE[y.dtype], N,
+              _lib.ptr(sc), _lib.ptr(sh), int(norm[4]) if norm is not None else 0,
+              _lib.ptr(out2), out2.stride(0) if out2 is not None else 0, _lib.ptr(part), _lib.stream())
+    return _gn_tagged(y, part, B, Ho, Wo, N) if is_conv else result(y)
 
 
 def conv2d_wq(x: torch.Tensor, pw: PackedWeight, kh, kw, stride, pad, upsample=False, geglu_rows=False):
@@ -1007,29 +973,14 @@ def conv2d_wq(x: torch.Tensor, pw: PackedWeight, kh, kw, stride, pad, upsample=F
     rows are interleaved (QuantLayer.geglu_rows) and the output comes back in the reference's column order.  N > 8."""
     w_img, Kp = pw.natural()
     N = pw.N
-    is_conv = x.dim() == 4 and pw.K == kh * kw * x.shape[1]
-    if is_conv:
-        B, C, H, W = x.shape
-        if upsample:
-            H, W = 2 * H, 2 * W
-        xs = x.contiguous(memory_format=torch.channels_last)
-        Ho = (H + 2 * pad - kh) // stride + 1
-        Wo = (W + 2 * pad - kw) // stride + 1
-        y = torch.empty((B * Ho * Wo, N), dtype=x.dtype, device=x.device)
-        _lib_call("dgq_conv2d_wq", _lib.ptr(xs), _lib.DTYPE_CODE[x.dtype], B, H, W, C, kh, kw, stride, pad, int(upsample),
-                  _lib.ptr(w_img), pw.bits, Kp, _lib.ptr(pw.alpha), _lib.ptr(pw.zp_true), _lib.ptr(pw.bias), N, int(geglu_rows),
-                  _lib.ptr(y), _lib.DTYPE_CODE[y.dtype], N, _lib.stream())
-        return y.view(B, Ho, Wo, N).permute(0, 3, 1, 2)
-    K = x.shape[-1]
-    assert pw.K == K and kh == kw == 1 and not upsample, "dgq conv2d_wq: weight [N][%d] does not match input %s" % (pw.K, tuple(x.shape))
-    x2 = x.reshape(-1, K)
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
-    y = torch.empty((x2.shape[0], N), dtype=x.dtype, device=x.device)
-    _lib_call("dgq_conv2d_wq", _lib.ptr(x2), _lib.DTYPE_CODE[x.dtype], x2.shape[0], 1, 1, K, 1, 1, 1, 0, 0,
+    xs, geom, result = _weight_only_operand(x, pw.K, kh, kw, stride, pad, upsample, "conv2d_wq")
+    B, H, W = geom[:3]
+    M = B * ((H + 2 * pad - kh) // stride + 1) * ((W + 2 * pad - kw) // stride + 1)
+    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    _lib_call("dgq_conv2d_wq", _lib.ptr(xs), _lib.DTYPE_CODE[x.dtype], *geom, int(upsample),
               _lib.ptr(w_img), pw.bits, Kp, _lib.ptr(pw.alpha), _lib.ptr(pw.zp_true), _lib.ptr(pw.bias), N, int(geglu_rows),
               _lib.ptr(y), _lib.DTYPE_CODE[y.dtype], N, _lib.stream())
-    return y.view(*x.shape[:-1], N)
+    return result(y)
 
 
 # ------------------------------------------------------------------------------------------ attention side

@@ -40,6 +40,33 @@ def natural_kperm(C: int, taps: int):
     return perm
 
 
+def natural_ksrc(C: int, kh: int, kw: int, Kp: int):
+    """ksrc (see ActLayout) of the natural physical order kp = tap·C + c, -1 from kh·kw·C to Kp."""
+    kp = torch.arange(Kp)
+    tap, c = kp // C, kp % C
+    e = ((tap // kw) << 24) | ((tap % kw) << 16) | c
+    return torch.where(kp < kh * kw * C, e, torch.full_like(e, -1)).to(torch.int32)
+
+
+def ksrc_index(ksrc: torch.Tensor, row_pitch: int, col_pitch: int):
+    """The decoder of the packed word (dh<<24)|(dw<<16)|c that plan_act writes: (dh·row_pitch + dw)·col_pitch + c of every packed
+    position as int32, -1 where ksrc < 0 (padding).  The pitches say what is addressed: (W, ldc) the input tensor, (kw, C) a
+    [tap][C] strip, (PW, C) a PW pixels wide input patch."""
+    e = ksrc
+    idx = (((e >> 24) & 0x7F) * row_pitch + ((e >> 16) & 0xFF)) * col_pitch + (e & 0xFFFF)
+    return torch.where(e >= 0, idx, torch.full_like(idx, -1)).to(torch.int32).contiguous()
+
+
+def ksrc_inverse(ksrc: torch.Tensor, kw: int, C: int, taps: int):
+    """inverse of ksrc: the packed position kp of element (tap, c) at [tap·C + c], [taps·C] int32; ksrc must cover every element"""
+    idx = ksrc_index(ksrc, kw, C)
+    valid = idx >= 0
+    out = torch.full((taps * C,), -1, dtype=torch.int32, device=ksrc.device)
+    out[idx[valid].long()] = torch.nonzero(valid).flatten().to(torch.int32)
+    assert int((out < 0).sum()) == 0, "per-K table does not cover every (tap, channel)"
+    return out.contiguous()
+
+
 @dataclass
 class ActLayout:
     """What one activation quantizer looks like to the kernels."""

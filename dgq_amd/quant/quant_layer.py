@@ -459,6 +459,20 @@ class QuantLayer(nn.Module):
     def taps(self):
         return self.w.shape[2] * self.w.shape[3] if self.is_conv else 1
 
+    def _conv_geom(self):
+        """(kh, kw, stride, pad) as the library entries take them; (1, 1, 1, 0) for a Linear layer"""
+        if not self.is_conv:
+            return 1, 1, 1, 0
+        return self.w.shape[2], self.w.shape[3], self.fwd_kwargs["stride"][0], self.fwd_kwargs["padding"][0]
+
+    def _plain(self) -> bool:
+        """a Linear layer, or a convolution with dilation 1 and groups 1 (what the library's conv entries compute)"""
+        return not self.is_conv or (tuple(self.fwd_kwargs.get("dilation", (1, 1)))[0] == 1 and self.fwd_kwargs.get("groups", 1) == 1)
+
+    def _has_act_table(self) -> bool:
+        """the activation quantizer is initialised, or the live timestep slot has a table"""
+        return bool(self.aqtizer.init or (self._slot_ref is not None and self._slot_ref.slot in self._act_tables))
+
     # -- weights ------------------------------------------------------------------------------------
     def _weight_key(self):
         q = self.wqtizer
@@ -558,18 +572,14 @@ class QuantLayer(nn.Module):
             b = self.original_b.to(device=x.device, dtype=x.dtype) if self.original_b is not None else None
             if quant_act:
                 x = self.aqtizer(x)
-            if (FP_STATE_HIP and x.is_cuda and x.dtype in ops.FLOAT_DTYPES and not torch.is_grad_enabled()
-                    and (not self.is_conv or (tuple(self.fwd_kwargs.get("dilation", (1, 1)))[0] == 1 and self.fwd_kwargs.get("groups", 1) == 1))):
+            if (FP_STATE_HIP and x.is_cuda and x.dtype in ops.FLOAT_DTYPES and not torch.is_grad_enabled() and self._plain()):
                 # FP state on the GPU without autograd (conv_in / conv_out of every quantized model, quant_model.py:66-73): the
                 # library's exact-fp32 kernel instead of MIOpen / rocBLAS (conv_out's four output channels take its N <= 8 form;
                 # step 9.537 vs 9.559 ms with MIOpen)
                 self._fp_natural(x.device)
-                if self.is_conv:
-                    # (gn_out: conv_in's output carries its GroupNorm partials on this path too — with or without an output redirect
-                    # the first resnet's norm1 and the last up resnet's see the same statistics)
-                    return ops.conv2d_f32w(x, self._wnat_fp[1], self._wnat_fp[2], self.w.shape[2], self.w.shape[3],
-                                           self.fwd_kwargs["stride"][0], self.fwd_kwargs["padding"][0], gn_out=True)
-                return ops.conv2d_f32w(x, self._wnat_fp[1], self._wnat_fp[2], 1, 1, 1, 0)
+                # (gn_out: conv_in's output carries its GroupNorm partials on this path too — with or without an output redirect
+                # the first resnet's norm1 and the last up resnet's see the same statistics)
+                return ops.conv2d_f32w(x, self._wnat_fp[1], self._wnat_fp[2], *self._conv_geom(), gn_out=self.is_conv)
             if self.is_conv:
                 return F.conv2d(x, w, b, stride=self.fwd_kwargs["stride"], padding=self.fwd_kwargs["padding"])
             return F.linear(x, w, b)
@@ -586,26 +596,18 @@ class QuantLayer(nn.Module):
                 if self.is_conv:
                     w = w.contiguous(memory_format=torch.channels_last)
             else:
-                if (WEIGHT_ONLY_HIP and x.dtype in ops.FLOAT_DTYPES and not (torch.is_grad_enabled() and x.requires_grad)
-                        and (not self.is_conv or (tuple(self.fwd_kwargs.get("dilation", (1, 1)))[0] == 1 and self.fwd_kwargs.get("groups", 1) == 1))):
-                    # inference in the weight-only state: exact-fp32 MFMA kernel of this library, not F.linear / F.conv2d of the
-                    # vendor libraries — from the packed codes (dgq_conv2d_wq), or on the dequantised fp32 weight (dgq_conv2d_f32w)
-                    if WEIGHT_ONLY_PACKED and self.w.shape[0] > 8:
-                        if self.is_conv:
-                            return ops.conv2d_wq(x, self.packed_weight(), self.w.shape[2], self.w.shape[3], self.fwd_kwargs["stride"][0],
-                                                 self.fwd_kwargs["padding"][0], geglu_rows=self.geglu_rows)
-                        return ops.conv2d_wq(x, self.packed_weight(), 1, 1, 1, 0, geglu_rows=self.geglu_rows)
-                    wn, bn = self.dequantized_weight_natural()
-                    if self.is_conv:
-                        return ops.conv2d_f32w(x, wn, bn, self.w.shape[2], self.w.shape[3], self.fwd_kwargs["stride"][0],
-                                               self.fwd_kwargs["padding"][0])
-                    return ops.conv2d_f32w(x, wn, bn, 1, 1, 1, 0)
+                # inference in the weight-only state: exact-fp32 MFMA kernel of this library, not F.linear / F.conv2d of the
+                # vendor libraries — from the packed codes (dgq_conv2d_wq), or on the dequantised fp32 weight (dgq_conv2d_f32w)
+                if self.on_packed_weight_only_path(x):
+                    return ops.conv2d_wq(x, self.packed_weight(), *self._conv_geom(), geglu_rows=self.geglu_rows)
+                if self._weight_only_hip(x):
+                    return ops.conv2d_f32w(x, *self.dequantized_weight_natural(), *self._conv_geom())
                 w = self.dequantized_weight(x.dtype)
             b = self.b.to(x.dtype) if self.b is not None else None
             if self.is_conv:
                 return F.conv2d(x, w, b, stride=self.fwd_kwargs["stride"], padding=self.fwd_kwargs["padding"])
             return F.linear(x, w, b)
-        if not self.aqtizer.init and not (self._slot_ref is not None and self._slot_ref.slot in self._act_tables):
+        if not self._has_act_table():
             self.aqtizer.init_from(x)           # first-forward self-initialisation (quant_layer.py:274-278)
         if self.aqtizer.calibrating():          # DGQ calibration: statistics of what the quantizer sees (:284-293, :630-641)
             seen = x
@@ -615,9 +617,7 @@ class QuantLayer(nn.Module):
             self.aqtizer.observe(seen)
         ab = self._binding()
         if self.is_conv:
-            kh, kw = self.w.shape[2], self.w.shape[3]
-            return _tap(self, ops.quant_conv2d(x, ab, kh, kw, self.fwd_kwargs["stride"][0], self.fwd_kwargs["padding"][0]),
-                        x=x, prologue=False)
+            return _tap(self, ops.quant_conv2d(x, ab, *self._conv_geom()), x=x, prologue=False)
         y = ops.quant_linear(x, ab)
         if self.geglu_rows:                     # the plain path returns the reference's column order
             y = y.index_select(-1, self._row_unperm(y.device))
@@ -628,8 +628,7 @@ class QuantLayer(nn.Module):
         (None, None): asked only by the calls whose result IS their module's result (``final=True``)."""
         if ops.pending_redirect() is None or not self.is_conv or x.dim() != 4:
             return None, None
-        kh, kw = self.w.shape[2], self.w.shape[3]
-        st, pd = self.fwd_kwargs["stride"][0], self.fwd_kwargs["padding"][0]
+        kh, kw, st, pd = self._conv_geom()
         Ho = (x.shape[2] * scale + 2 * pd - kh) // st + 1
         Wo = (x.shape[3] * scale + 2 * pd - kw) // st + 1
         return ops.take_redirect(x.shape[0] * Ho * Wo, self.w.shape[0], x.dtype)
@@ -639,17 +638,14 @@ class QuantLayer(nn.Module):
         pending ops.OutputRedirect is honoured on the plain path — integer path or FP state of a convolution, no tap, no hooks."""
         if (ops.pending_redirect() is not None and self.is_conv and x.is_cuda and x.dtype in ops.FLOAT_DTYPES and LAYER_TAP is None and not self.aqtizer.calibrating()
                 and not self._forward_hooks and not self._forward_pre_hooks and not torch.is_grad_enabled()):
-            kh, kw = self.w.shape[2], self.w.shape[3]
-            st, pd = self.fwd_kwargs["stride"][0], self.fwd_kwargs["padding"][0]
             if self.on_integer_path(x):
                 out, out2 = self._take_redirect(x)
-                return ops.quant_conv2d(x, self._binding(), kh, kw, st, pd, out=out, out2=out2)
-            if (not self.use_wq and not (self.use_aq and not self.disable_aq) and FP_STATE_HIP
-                    and tuple(self.fwd_kwargs.get("dilation", (1, 1)))[0] == 1 and self.fwd_kwargs.get("groups", 1) == 1):
+                return ops.quant_conv2d(x, self._binding(), *self._conv_geom(), out=out, out2=out2)
+            if (not self.use_wq and not (self.use_aq and not self.disable_aq) and FP_STATE_HIP and self._plain()):
                 out, out2 = self._take_redirect(x)
                 if out is None:                                   # (the FP kernel takes the second copy only)
                     self._fp_natural(x.device)
-                    return ops.conv2d_f32w(x, self._wnat_fp[1], self._wnat_fp[2], kh, kw, st, pd, out2=out2, gn_out=True)
+                    return ops.conv2d_f32w(x, self._wnat_fp[1], self._wnat_fp[2], *self._conv_geom(), out2=out2, gn_out=True)
                 ops.pending_redirect().taken = False
         return self(x)
 
@@ -661,27 +657,25 @@ class QuantLayer(nn.Module):
         (ops.conv2d_wq(upsample=True)), under the same conditions."""
         if (LAYER_TAP is None and self.is_conv and self.on_packed_weight_only_path(x) and not self.aqtizer.calibrating()
                 and not self._forward_hooks and not self._forward_pre_hooks):
-            return ops.conv2d_wq(x, self.packed_weight(), self.w.shape[2], self.w.shape[3], self.fwd_kwargs["stride"][0],
-                                 self.fwd_kwargs["padding"][0], upsample=True)
+            return ops.conv2d_wq(x, self.packed_weight(), *self._conv_geom(), upsample=True)
         if (LAYER_TAP is None and self.is_conv and self.on_integer_path(x) and x.dtype in ops.FLOAT_DTYPES and not self.aqtizer.calibrating()
-                and not self._forward_hooks and not self._forward_pre_hooks and self.w.shape[2] * self.w.shape[3] > 1):
-            kh, kw = self.w.shape[2], self.w.shape[3]
+                and not self._forward_hooks and not self._forward_pre_hooks and self.taps > 1):
             out, out2 = self._take_redirect(x, 2) if final else (None, None)
-            return ops.quant_conv2d(x, self._binding(), kh, kw, self.fwd_kwargs["stride"][0], self.fwd_kwargs["padding"][0], upsample=True,
-                                    out=out, out2=out2)
+            return ops.quant_conv2d(x, self._binding(), *self._conv_geom(), upsample=True, out=out, out2=out2)
         return self(F.interpolate(x, scale_factor=2.0, mode="nearest"))
 
     def on_packed_weight_only_path(self, x: torch.Tensor) -> bool:
         """True when forward(x) would run dgq_conv2d_wq (weight-only state from the packed codes, GPU, outside autograd)."""
-        return (WEIGHT_ONLY_HIP and WEIGHT_ONLY_PACKED and self.use_wq and not (self.use_aq and not self.disable_aq) and x.is_cuda
-                and x.dtype in ops.FLOAT_DTYPES and not getattr(self.wqtizer, "soft_tgt", False)
-                and not (torch.is_grad_enabled() and x.requires_grad) and self.w.shape[0] > 8
-                and (not self.is_conv or (tuple(self.fwd_kwargs.get("dilation", (1, 1)))[0] == 1 and self.fwd_kwargs.get("groups", 1) == 1)))
+        return (WEIGHT_ONLY_PACKED and self.use_wq and not (self.use_aq and not self.disable_aq) and x.is_cuda
+                and not getattr(self.wqtizer, "soft_tgt", False) and self.w.shape[0] > 8 and self._weight_only_hip(x))
+
+    def _weight_only_hip(self, x: torch.Tensor) -> bool:
+        """what the weight-only state asks of x and of the layer before it leaves F.conv2d / F.linear for this library's kernels"""
+        return WEIGHT_ONLY_HIP and x.dtype in ops.FLOAT_DTYPES and not (torch.is_grad_enabled() and x.requires_grad) and self._plain()
 
     def on_integer_path(self, x: torch.Tensor) -> bool:
         """True when forward(x) would run dgq_quant_act + dgq_gemm_wxa8 (weights and activations quantised, GPU)."""
-        return (self.use_wq and self.use_aq and not self.disable_aq and x.is_cuda
-                and (self.aqtizer.init or (self._slot_ref is not None and self._slot_ref.slot in self._act_tables)))
+        return self.use_wq and self.use_aq and not self.disable_aq and x.is_cuda and self._has_act_table()
 
     def forward_fused(self, x: torch.Tensor, pre_act: int = 0, residual=None, fq=None, ln=None, geglu: bool = False) -> torch.Tensor:
         """``fq(self(act(x))) + residual`` with the elementwise pieces folded into the two kernels of the layer:
@@ -721,17 +715,14 @@ class QuantLayer(nn.Module):
     def can_fuse_prenorm(self, x: torch.Tensor) -> bool:
         """True when this layer runs on the integer path, so a preceding GroupNorm(+SiLU) can be folded into its
         quantise-on-load pass (dgq_groupnorm_scale_shift + dgq_quant_act prologue)."""
-        return (self.is_conv and self.use_wq and self.use_aq and not self.disable_aq and x.is_cuda
-                and x.dtype in ops.FLOAT_DTYPES
-                and (self.aqtizer.init or (self._slot_ref is not None and self._slot_ref.slot in self._act_tables)))
+        return self.is_conv and self.on_integer_path(x) and x.dtype in ops.FLOAT_DTYPES
 
     def forward_prenorm(self, x: torch.Tensor, norm: nn.GroupNorm, silu: bool = True, residual=None, bias_rows=None, final: bool = False) -> torch.Tensor:
         """conv(act(GroupNorm(x))) [+ residual | + bias_rows[b, :, None, None]] without materialising the normalised tensor.
         final: the result is the calling module's own result (a pending ops.OutputRedirect may place it)."""
         ab = self._binding()
-        kh, kw = self.w.shape[2], self.w.shape[3]
         out, out2 = self._take_redirect(x) if (final and LAYER_TAP is None) else (None, None)
-        return _tap(self, ops.quant_conv2d(x, ab, kh, kw, self.fwd_kwargs["stride"][0], self.fwd_kwargs["padding"][0],
+        return _tap(self, ops.quant_conv2d(x, ab, *self._conv_geom(),
                                            norm=(norm.num_groups, norm.eps, norm.weight, norm.bias, 1 if silu else 0),
                                            residual=residual, bias_rows=bias_rows, out=out, out2=out2),
                     x=x, prologue=True, residual=residual, bias_rows=bias_rows)
@@ -741,9 +732,7 @@ class QuantLayer(nn.Module):
     #    GroupNorm in front of proj_in folds into its quantise-on-load pass, the residual behind proj_out into its GEMM epilogue,
     #    and proj_out leaves GroupNorm partials for the next resnet block — as the Conv2d projections of SD do.
     def can_fuse_tokens(self, x: torch.Tensor) -> bool:
-        return (not self.is_conv and self.w.dim() == 2 and self.use_wq and self.use_aq and not self.disable_aq and x.is_cuda
-                and x.dtype in ops.FLOAT_DTYPES
-                and (self.aqtizer.init or (self._slot_ref is not None and self._slot_ref.slot in self._act_tables)))
+        return not self.is_conv and self.w.dim() == 2 and self.on_integer_path(x) and x.dtype in ops.FLOAT_DTYPES
 
     def forward_prenorm_tokens(self, x: torch.Tensor, norm: nn.GroupNorm) -> torch.Tensor:
         """Linear(GroupNorm(x).permute(0, 2, 3, 1).reshape(B, HW, C)) for x [B, C, H, W] -> [B, HW, N]."""
@@ -770,13 +759,11 @@ class QuantLayer(nn.Module):
         dgq_conv2d_f32w."""
         return (FP_STATE_HIP and self.is_conv and not self.use_wq and not (self.use_aq and not self.disable_aq) and x.is_cuda
                 and not self._forward_hooks and not self._forward_pre_hooks     # (data capture hooks must see a plain call)
-                and x.dtype in ops.FLOAT_DTYPES and not torch.is_grad_enabled()
-                and tuple(self.fwd_kwargs.get("dilation", (1, 1)))[0] == 1 and self.fwd_kwargs.get("groups", 1) == 1)
+                and x.dtype in ops.FLOAT_DTYPES and not torch.is_grad_enabled() and self._plain())
 
     def forward_prenorm_fp(self, x: torch.Tensor, norm: nn.GroupNorm, silu: bool = True) -> torch.Tensor:
         wn, bn = self._fp_natural(x.device)
-        return ops.conv2d_f32w(x, wn, bn, self.w.shape[2], self.w.shape[3], self.fwd_kwargs["stride"][0], self.fwd_kwargs["padding"][0],
-                               norm=(norm.num_groups, norm.eps, norm.weight, norm.bias, 1 if silu else 0))
+        return ops.conv2d_f32w(x, wn, bn, *self._conv_geom(), norm=(norm.num_groups, norm.eps, norm.weight, norm.bias, 1 if silu else 0))
 
     def _fp_natural(self, device):
         key = (self.original_w.data_ptr(), self.original_w._version, str(device))
@@ -792,10 +779,8 @@ class QuantLayer(nn.Module):
         """conv(x) + residual with the add in the GEMM epilogue (integer path), else unfused.
         final: the result is the calling module's own result (a pending ops.OutputRedirect may place it)."""
         if self.is_conv and self.on_integer_path(x) and x.dtype in ops.FLOAT_DTYPES:
-            kh, kw = self.w.shape[2], self.w.shape[3]
             out, out2 = self._take_redirect(x) if (final and LAYER_TAP is None) else (None, None)
-            return _tap(self, ops.quant_conv2d(x, self._binding(), kh, kw, self.fwd_kwargs["stride"][0],
-                                               self.fwd_kwargs["padding"][0], residual=residual, out=out, out2=out2),
+            return _tap(self, ops.quant_conv2d(x, self._binding(), *self._conv_geom(), residual=residual, out=out, out2=out2),
                         x=x, prologue=False, residual=residual)
         return self(x) + residual
 

@@ -904,13 +904,22 @@ def test_linear_smallm_batch_equals_the_gemm_path(M, K, wbits, abits, dtype, dev
         assert torch.equal(y, ref), (ab.pw.N, (y.float() - ref.float()).abs().max().item())
 
 
+@pytest.mark.parametrize("fuse", [True, False, "all"], ids=["fuse", "two-launch", "fuse-all"])
 @pytest.mark.parametrize("M,K,with_ln", [(154, 768, False), (512, 320, True), (64, 1280, True)])
-def test_quant_linear_multi_equals_single_calls(M, K, with_ln, dev):
+def test_quant_linear_multi_equals_single_calls(M, K, with_ln, fuse, dev, monkeypatch):
     """dgq_quant_act_batch + dgq_gemm_wxa8_batch (layers sharing one input: q/k/v, the cross-attention k/v of the text
     context) against one dgq_quant_act + dgq_gemm_wxa8 per layer: same kernels, same arithmetic -> bit-identical,
-    for mixed per-K (grouped) and per-token / scalar tables and mixed widths in one call."""
+    for mixed per-K (grouped) and per-token / scalar tables and mixed widths in one call.  ``fuse``: ops.GEMM_FUSE on — the form
+    the planner picks — and off — the two-launch form everywhere; the planner declines quantise-on-load below 2048 rows, so
+    "fuse-all" (DGQ_GEMM_FUSE_ALL=1: wherever the panel fits) is what runs the quantise-on-load batches at these shapes."""
     from dgq_amd import ops, synth
     from dgq_amd.plan import plan_act
+    monkeypatch.setattr(ops, "GEMM_FUSE", bool(fuse))
+    monkeypatch.delenv("DGQ_GEMM_FORCE", raising=False)
+    if fuse == "all":
+        monkeypatch.setenv("DGQ_GEMM_FUSE_ALL", "1")
+    else:
+        monkeypatch.delenv("DGQ_GEMM_FUSE_ALL", raising=False)
     g = torch.Generator().manual_seed(M + K)
     x = torch.randn(2, M // 2, K, generator=g).to(dev)
     ln = None
@@ -931,6 +940,8 @@ def test_quant_linear_multi_equals_single_calls(M, K, with_ln, dev):
         else:
             lay = plan_act(torch.tensor(0.03), torch.tensor(120.0), "linear", K, 1, 8)
         binds.append(ops.ActBinding(lay, pw, 8))
+    if fuse == "all":
+        assert ops._multi_fuses(binds, M, K, x.dtype, x.reshape(-1, K)), "fuse-all no longer takes the quantise-on-load batches"
     outs = ops.quant_linear_multi(x, binds, ln=ln)
     for ab, y in zip(binds, outs):
         ref = ops.quant_linear(x, ab, ln=ln)

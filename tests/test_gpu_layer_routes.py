@@ -72,12 +72,9 @@ def quantiser_route(B, H, W, C, k, stride, pad, Kp, per_k, L, bits, ups=False, p
     if ln:
         a.ln_gamma, a.ln_beta, a.ln_eps = DUMMY, DUMMY, 1e-5
     a.ups, a.ksplits, a.codes, a.rowsum = 1 if ups else 0, 1, DUMMY, DUMMY
-    parts = 1
-    if (a.kdst is None and a.kpat is None) or lib.dgq_quant_act_variant(ctypes.byref(a)) not in (3, 4, 5):
-        if ups:
-            return None
-        parts = ops.act_ksplits(M, Kp)
-        a.ksplits = parts
+    parts = ops.quant_splits(a, M)                 # the rule of ops.quant_act and ops.quant_linear_multi itself
+    if parts is None:
+        return None
     v = lib.dgq_quant_act_variant(ctypes.byref(a))
     return v, parts, (tile if v == 5 else 0), (partial if v == 5 else False)
 

@@ -107,6 +107,66 @@ def test_plan_layout_classification_and_natural_order():
         plan_act(torch.rand(1, 1, 65) + 0.1, torch.zeros(1, 1, 65), "linear", 64, 1, 8)
 
 
+def _perk_conv_layout(C, taps, kw, sizes):
+    """a per-K conv layout whose (δ, z) groups have the given sizes, dealt over the reference K order k = c·taps + tap in a fixed shuffle"""
+    K = C * taps
+    assert sum(sizes) == K
+    group = torch.repeat_interleave(torch.arange(len(sizes)), torch.tensor(sizes))[torch.randperm(K, generator=torch.Generator().manual_seed(K))]
+    d, z = 0.01 * (1 + group.float()), 100.0 + group.float()
+    return plan_act(d.view(1, -1, 1), z.view(1, -1, 1), "conv", C, taps, 8, kw=kw)
+
+
+def _source_of(lay, kp, taps, kw):
+    """(dh, dw, c) of packed position kp, from kperm (k_ref = c·taps + tap) — not from ksrc"""
+    c, tap = divmod(int(lay.kperm[kp]), taps)
+    return tap // kw, tap % kw, c
+
+
+@pytest.mark.parametrize("C,taps,kw,sizes", [(8, 9, 3, (30, 25, 17)), (8, 3, 3, (11, 7, 6))], ids=["3x3", "1x3"])
+def test_ksrc_index_matches_a_plain_loop(C, taps, kw, sizes):
+    """plan.ksrc_index on every packed position for the three pitch pairs ActBinding asks for — the input tensor (W, ldc), the
+    [tap][C] strip (kw, C), the input patch (PW, C) — against the position's source element taken from kperm; padding gives -1.
+    The 1 x 3 kernel (taps = 3, kw = 3) has dh = 0 throughout: a decoder that swapped dh and dw fails on it."""
+    from dgq_amd.plan import ksrc_index
+    lay = _perk_conv_layout(C, taps, kw, sizes)
+    assert lay.Kp == 128 and lay.n_groups == 3 and int((lay.kperm < 0).sum()) == 128 - C * taps
+    for rp, cp in ((5, 8), (kw, C), (10, C)):
+        got = ksrc_index(lay.ksrc, rp, cp)
+        assert got.dtype == torch.int32 and got.shape == (lay.Kp,)
+        for kp in range(lay.Kp):
+            if lay.kperm[kp] < 0:
+                assert int(got[kp]) == -1, (rp, cp, kp)
+            else:
+                dh, dw, c = _source_of(lay, kp, taps, kw)
+                assert int(got[kp]) == (dh * rp + dw) * cp + c, (rp, cp, kp)
+
+
+def test_natural_ksrc_is_the_natural_order():
+    """natural_ksrc(8, 3, 3, 128) under a PW-wide patch: ((tap // 3)·PW + tap % 3)·C + c at kp = tap·C + c < 72, -1 above"""
+    from dgq_amd.plan import ksrc_index, natural_ksrc
+    C, PW = 8, 10
+    got = ksrc_index(natural_ksrc(C, 3, 3, 128), PW, C)
+    assert got.dtype == torch.int32 and got.shape == (128,)
+    for kp in range(128):
+        tap, c = divmod(kp, C)
+        assert int(got[kp]) == (((tap // 3) * PW + tap % 3) * C + c if kp < 72 else -1), kp
+
+
+def test_ksrc_inverse_is_the_permutation_of_the_layout():
+    """plan.ksrc_inverse (ActBinding.kdst): entry (tap, c) is the one packed position whose source element is (tap, c)"""
+    from dgq_amd.plan import ksrc_inverse
+    C, taps, kw = 8, 9, 3
+    lay = _perk_conv_layout(C, taps, kw, (30, 25, 17))
+    kd = ksrc_inverse(lay.ksrc, kw, C, taps)
+    assert kd.dtype == torch.int32 and kd.shape == (taps * C,)
+    assert sorted(kd.tolist()) == sorted(torch.nonzero(lay.kperm >= 0).flatten().tolist())
+    for tap in range(taps):
+        for c in range(C):
+            assert int(lay.kperm[int(kd[tap * C + c])]) == c * taps + tap, (tap, c)
+    with pytest.raises(AssertionError):
+        ksrc_inverse(torch.where(torch.arange(lay.Kp) == int(kd[0]), torch.tensor(-1, dtype=torch.int32), lay.ksrc), kw, C, taps)
+
+
 # ------------------------------------------------------------------------------------------ FP graph + oracle structure
 @pytest.mark.parametrize("arch", ["tiny"])
 def test_fp_graph_matches_oracle_structure(arch):
