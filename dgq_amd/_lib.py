@@ -43,6 +43,8 @@ SIGNATURES = {
     "dgq_linear_smallm_batch": [_vp, _i, _i, _i, _i64, _i, _i, _vp, _i, _vp],
     "dgq_quant_act_batch": [_i, _vp, _vp],
     "dgq_quant_act_variant": [_vp],
+    "dgq_act_row_params": [_vp, _i, _vp, ctypes.c_size_t, _vp, _vp, _vp],
+    "dgq_act_row_params_batch": [_i, _vp, _vp, _vp],
     "dgq_quant_act_conv_tile": [_i, _i, _i, _i, _i, _vp],
     "dgq_gemm_wxa8_batch": [_i, _vp, _vp],
     "dgq_adaround_soft_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
@@ -88,6 +90,11 @@ class QuantActArgs(ctypes.Structure):
                 ("pad", _i), ("ksrc", _vp), ("koff", _vp), ("klds", _vp), ("kdst", _vp), ("Kp", _i), ("per_m", _i), ("delta", _vp), ("zp", _vp),
                 ("L", _i), ("bits", _i), ("codes", _vp), ("rowsum", _vp), ("ksplits", _i), ("pre_scale", _vp), ("pre_shift", _vp),
                 ("pre_act", _i), ("ln_gamma", _vp), ("ln_beta", _vp), ("ln_eps", _f), ("kpat", _vp), ("ups", _i)]
+
+
+class RowParamsOut(ctypes.Structure):
+    """dgq_act_rowparams_out_t of include/dgq_hip.h"""
+    _fields_ = [("fold_T", _i), ("ws", _vp), ("ws_floats", ctypes.c_size_t), ("delta", _vp), ("zp", _vp)]
 
 
 class GemmArgs(ctypes.Structure):

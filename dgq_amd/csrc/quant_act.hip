@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include "dgq_common.h"
 #include "quant_common.h"
+#include "quant_prologue.h"
 #include "diag.h"
 
 DGQ_DIAG_BUFFER(quant)
@@ -51,39 +52,6 @@ struct QuantActBatch {
 #define DGQ_QA_SHARE 4
 
 
-
-// LayerNorm statistics of one row of C <= 2048 elements (C % 4 == 0), computed by the wave that quantises the row: the
-// row is read ONCE into registers (8 float4 per lane), mean first, then Σ(x − mean)² from the registers; biased
-// variance, rstd = 1/sqrt(var + eps) as nn.LayerNorm.
-#define DGQ_LN_MAX_C 2048
-template <typename TIn>
-__device__ __forceinline__ void row_layernorm_stats(const TIn* xr, int C, float eps, int lane, float& mu, float& rstd) {
-    float v[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = lane * 4 + 256 * i;
-        if (c < C) load4<TIn>(xr + c, v[i]);
-        else v[i][0] = v[i][1] = v[i][2] = v[i][3] = 0.0f;
-    }
-    float s = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    mu = s / (float)C;
-    float q = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = lane * 4 + 256 * i;
-        if (c < C) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) q += (v[i][j] - mu) * (v[i][j] - mu);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-    rstd = 1.0f / sqrtf(q / (float)C + eps);
-}
 
 // One wave per output row; each lane owns 4 consecutive kp per 256-wide step (one packed dword), so that the
 // table read (int4), the gathered loads (lane stride 16 B within a (group, tap) run) and the code store (256 B per

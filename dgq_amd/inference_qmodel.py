@@ -45,6 +45,9 @@ def parse_args(argv=None):
     p.add_argument("--n_prompts", type=int, default=2, help="synthetic prompts (the reference renders 2 images)")
     p.add_argument("--out", default="latents_{rank}.pt")
     p.add_argument("--graphs", action="store_true", help="replay one hipGraph per timestep slot")
+    p.add_argument("--aq_real_time", action="store_true",
+                   help="with --use_aq: per-row activation parameters taken from every call's own rows (Scaler.MINMAX per row, "
+                        "dgq_act_row_params) — runs from a weight-only checkpoint, no activation calibration")
     return p.parse_args(argv)
 
 
@@ -71,13 +74,17 @@ def main(argv=None):
     res = ARCH[mt]["sample_size"]
     batch = 2 if guidance > 0 else 1
     ckpt = opt.cali_ckpt
+    real_time = opt.use_aq and opt.aq_real_time
+    if opt.aq_real_time and not opt.use_aq:
+        raise SystemExit("--aq_real_time is a mode of the activation quantizers: it needs --use_aq")
     if ckpt is None:
-        ckpt = "/tmp/dgq_cli_%s_w%da%dg%d_s%d.pth" % (mt, opt.wq, opt.aq, opt.group_num if opt.use_group else 1, steps)
+        ckpt = "/tmp/dgq_cli_%s_w%da%dg%d_s%d%s.pth" % (mt, opt.wq, opt.aq, opt.group_num if opt.use_group else 1, steps,
+                                                       "_wonly" if real_time else "")
         if rank == 0 and not os.path.exists(ckpt):
             synth.write_cali_ckpt(ckpt, mt, opt.wq, opt.aq, opt.group_num if opt.use_group else 1,
                                   num_slots=steps if opt.time_aware_aqtizer else 1, seed=0, batch=batch, res=res,
                                   start_peak=opt.t2i_start_peak, uniform_softmax=opt.use_aq and not opt.t2i_log_quant,
-                                  with_act=opt.use_aq)
+                                  with_act=opt.use_aq and not real_time)
         if world > 1:
             import torch.distributed as dist
             dist.init_process_group("nccl")
@@ -85,6 +92,8 @@ def main(argv=None):
 
     wq_params = {"bits": opt.wq, "channel_wise": True, "scaler": Scaler.MINMAX}
     aq_params = {"bits": opt.aq, "channel_wise": False, "scaler": Scaler.MINMAX, "leaf_param": opt.use_aq}
+    if real_time:
+        aq_params["real_time"] = True
     softmax_aq_params = {"softmax_a_bit": opt.aq, "t2i_log_quant": opt.t2i_log_quant,
                          "t2i_real_time": opt.t2i_real_time, "t2i_start_peak": opt.t2i_start_peak, "log_max_1": False}
     time_aware = opt.time_aware_aqtizer if opt.use_aq else False

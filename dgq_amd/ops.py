@@ -186,6 +186,9 @@ class PackedWeight:
 class ActBinding:
     """Device-resident tables of one (layer, timestep-slot) activation quantizer."""
 
+    #: True on a DynamicActBinding whose row tables are not set yet (see there)
+    dynamic = False
+
     def _table(self, key, make):
         if key not in self._koff:
             self._koff[key] = make()
@@ -281,6 +284,35 @@ class ActBinding:
                     self._fill = torch.tensor([int(self._zc)] * 16 + [0] * 16, dtype=torch.int8, device=dev)
                 else:
                     self._zc, self._fill = None, None
+
+
+class DynamicActBinding(ActBinding):
+    """The binding of a real-time activation quantizer (UniformAffineQuantizer(real_time=True)): mode ``perM`` on the natural-order
+    weight image — one copy per layer, no K permutation, no timestep slots — whose row tables do not exist until the layer sees its
+    input.  quant_linear / quant_conv2d / quant_linear_multi / gemm_act ask dgq_act_row_params for one (δ, z) per row of THIS call's
+    operand and continue with ``bound(mdelta, mzp)``: a shallow copy with L = M and those tables, which every per-M route then reads as
+    mdelta[m % L] like a calibrated per-token table."""
+
+    dynamic = True
+
+    def __init__(self, pw: PackedWeight, abits: int):
+        self.mode, self.abits, self.offset = "perM", abits, act_offset(abits)
+        self.pw = pw
+        self.wpacked, self.Kp = pw.natural()
+        self.wfrag = pw.natural_frag()
+        self.ksrc = None
+        self._koff = {}
+        self.mdelta = self.mzp = None
+        self.L = 0
+        self.gamma = pw.bias
+        self.vn = pw.vn()
+
+    def bound(self, mdelta: torch.Tensor, mzp: torch.Tensor):
+        import copy
+        ab = copy.copy(self)                                # shares the weight images and the (geometry-keyed) table cache
+        ab.dynamic = False
+        ab.mdelta, ab.mzp, ab.L = mdelta, mzp, mdelta.numel()
+        return ab
 
 
 # ------------------------------------------------------------------------------------------ hot path
@@ -404,22 +436,14 @@ def groupnorm_from_partials(gn, groups, eps, gamma, beta):
     return scale, shift
 
 
-def _quant_args(x, geom, ab: ActBinding, pre=None, ln=None, ups=False):
-    """(dgq_quant_act_args_t, the tensors it points to) for the layer input x (channels-last storage) of geometry geom = (B, H, W, C,
-    kh, kw, stride, pad) under ab's tables — with one K split and placeholder outputs: the caller settles the split (quant_splits),
-    allocates and sets ``codes`` / ``rowsum``.  pre / ln / ups as in quant_act."""
+def _quant_input(x, geom, bits, pre=None, ln=None, ups=False):
+    """(dgq_quant_act_args_t, the tensors it points to) with the INPUT description of the layer input x (channels-last storage) of
+    geometry geom = (B, H, W, C, kh, kw, stride, pad) set — x, dtype, geometry, bits, the folded prologue — and nothing else: what
+    dgq_act_row_params reads, and what _quant_args completes with a binding's tables.  pre / ln / ups as in quant_act."""
     B, H, W, C, kh, kw, stride, pad = geom
-    per_m = 0 if ab.mode == "perK" else 1
-    ldc = 2 * C if (pre and pre[2] == 2) else C
     a = _lib.QuantActArgs()
     a.x, a.x_dtype, a.B, a.H, a.W, a.C, a.kh, a.kw, a.stride, a.pad = x.data_ptr(), _lib.DTYPE_CODE[x.dtype], B, H, W, C, kh, kw, stride, pad
-    a.ksrc, a.koff, a.klds, a.kdst = _dp(ab.ksrc), _dp(ab.koff(W, ldc)), _dp(ab.klds(kw, C)), _dp(ab.kdst(kw, C, kh * kw))
-    if kh * kw > 1 and C % 4 == 0:                           # the block-staged conv path, where the geometry has one
-        pw = ab.conv_patch_width(kh, kw, C, stride)
-        a.kpat = _dp(ab.kpat(kh, kw, C, pw)) if pw else None
-    a.Kp, a.per_m = ab.Kp, per_m
-    a.delta, a.zp = (ab.cdelta.data_ptr(), ab.czp.data_ptr()) if not per_m else (ab.mdelta.data_ptr(), ab.mzp.data_ptr())
-    a.L, a.bits = (1 if not per_m else ab.L), ab.abits
+    a.bits = bits
     keep = [x]
     if pre and pre[0] is not None:
         a.pre_scale, a.pre_shift = pre[0].data_ptr(), pre[1].data_ptr()
@@ -430,9 +454,73 @@ def _quant_args(x, geom, ab: ActBinding, pre=None, ln=None, ups=False):
         a.ln_gamma, a.ln_beta, a.ln_eps = g.data_ptr(), b.data_ptr(), float(ln[2])
         keep += [g, b]
     a.ups = 1 if ups else 0
+    return a, keep
+
+
+def _quant_args(x, geom, ab: ActBinding, pre=None, ln=None, ups=False):
+    """(dgq_quant_act_args_t, the tensors it points to) for the layer input x (channels-last storage) of geometry geom = (B, H, W, C,
+    kh, kw, stride, pad) under ab's tables — with one K split and placeholder outputs: the caller settles the split (quant_splits),
+    allocates and sets ``codes`` / ``rowsum``.  pre / ln / ups as in quant_act."""
+    B, H, W, C, kh, kw, stride, pad = geom
+    per_m = 0 if ab.mode == "perK" else 1
+    ldc = 2 * C if (pre and pre[2] == 2) else C
+    a, keep = _quant_input(x, geom, ab.abits, pre, ln, ups)
+    a.ksrc, a.koff, a.klds, a.kdst = _dp(ab.ksrc), _dp(ab.koff(W, ldc)), _dp(ab.klds(kw, C)), _dp(ab.kdst(kw, C, kh * kw))
+    if kh * kw > 1 and C % 4 == 0:                           # the block-staged conv path, where the geometry has one
+        pw = ab.conv_patch_width(kh, kw, C, stride)
+        a.kpat = _dp(ab.kpat(kh, kw, C, pw)) if pw else None
+    a.Kp, a.per_m = ab.Kp, per_m
+    a.delta, a.zp = (ab.cdelta.data_ptr(), ab.czp.data_ptr()) if not per_m else (ab.mdelta.data_ptr(), ab.mzp.data_ptr())
+    a.L = 1 if not per_m else ab.L
     a.ksplits = 1
     a.codes = a.rowsum = 1                                   # placeholders: dgq_quant_act_variant only validates non-NULL
     return a, keep
+
+
+def act_row_params_multi(problems):
+    """dgq_act_row_params_batch: the real-time row tables of up to 4 inputs of one dtype in shared launches.  problems: dicts / tuples
+    (x, geom, bits, pre, ln, ups, fold_T) — x the channels-last storage and geom = (B, H, W, C, kh, kw, stride, pad) as for quant_act,
+    fold_T > 0 folds the rows r with equal r % fold_T (Linear inputs).  Returns [(δ, z)] fp32 device tensors, [M] or [fold_T] each.
+    At most two launches, no synchronisation: capture-safe (the scratch comes from torch's allocator like every other temporary)."""
+    n = len(problems)
+    ins = (_lib.QuantActArgs * n)()
+    outs = (_lib.RowParamsOut * n)()
+    keep, res = [], []
+    for i, (x, geom, bits, pre, ln, ups, fold_T) in enumerate(problems):
+        B, H, W, C, kh, kw, stride, pad = geom
+        a, k = _quant_input(x, geom, bits, pre, ln, ups)
+        ins[i] = a
+        M = B * ((H + 2 * pad - kh) // stride + 1) * ((W + 2 * pad - kw) // stride + 1)
+        entries = fold_T if fold_T else M
+        d = torch.empty((entries,), dtype=torch.float32, device=x.device)
+        z = torch.empty((entries,), dtype=torch.float32, device=x.device)
+        o = outs[i]
+        o.fold_T, o.delta, o.zp = fold_T, d.data_ptr(), z.data_ptr()
+        if fold_T or (kh, kw, stride, pad) != (1, 1, 1, 0):
+            ws = torch.empty((2 * B * (H >> (1 if ups else 0)) * (W >> (1 if ups else 0)),), dtype=torch.float32, device=x.device)
+            o.ws, o.ws_floats = ws.data_ptr(), ws.numel()
+            k.append(ws)
+        keep += k
+        res.append((d, z))
+
+    def issue(_keep=keep):
+        _lib_call("dgq_act_row_params_batch", n, _c.cast(ins, _c.c_void_p), _c.cast(outs, _c.c_void_p), _lib.stream())
+    issue()
+    if ROWPARAMS_LAUNCH_HOOK is not None:
+        ROWPARAMS_LAUNCH_HOOK(issue, problems)
+    return res
+
+
+def act_row_params(x, geom, bits, pre=None, ln=None, ups=False, fold_T=0):
+    """(δ, z) of the real-time activation quantizer for every row of one layer input — see act_row_params_multi"""
+    return act_row_params_multi([(x, geom, bits, pre, ln, ups, fold_T)])[0]
+
+
+def _bind_rows(ab: ActBinding, x, geom, pre=None, ln=None, ups=False):
+    """ab itself, or — a DynamicActBinding — ab bound to the row tables of this call's operand"""
+    if not ab.dynamic:
+        return ab
+    return ab.bound(*act_row_params(x, geom, ab.abits, pre, ln, ups))
 
 
 def quant_splits(a, M):
@@ -553,6 +641,8 @@ def make_extra(residual=None, fq=None, res_div=1, geglu=False, gn_partial=None, 
 #: and the row sums it writes, which the algorithm does not need; ATTN_LAUNCH_HOOK(issue, flops, bytes): every dgq_attention call (its two or three kernels).
 QUANT_LAUNCH_HOOK = None
 ATTN_LAUNCH_HOOK = None
+#: ROWPARAMS_LAUNCH_HOOK(issue, problems): every dgq_act_row_params_batch call (the real-time row tables; problems as act_row_params_multi takes them)
+ROWPARAMS_LAUNCH_HOOK = None
 #: when set, every GEMM launch of the dgq_gemm_wxa8 family is issued through
 #: ``GEMM_LAUNCH_HOOK(issue, problems)`` — ``issue()`` launches it (again) on the current stream, ``problems`` lists the
 #: (M, ActBinding, out_element_size, input_bytes) of the layers the launch computes — input_bytes > 0 where the launch quantises its own
@@ -679,6 +769,9 @@ def _with_act(extra, ab: "ActBinding", M, act):
 
 def gemm_act(x2, M, ab: "ActBinding", out_dtype, extra=None, pre=None, ln=None, rows_per_image=1, out=None):
     """one launch: aqtizer(x2) @ Wᵀ with the layer's epilogue — dgq_gemm_wxa8 with quantise-on-load (see act_fuses)"""
+    if ab.dynamic:                                       # (a caller that did not bind the row tables itself)
+        assert x2.is_contiguous()
+        ab = _bind_rows(ab, x2, (M // rows_per_image, rows_per_image, 1, ab.pw.K, 1, 1, 1, 0), pre, ln)
     extra = _with_act(extra, ab, M, make_act(x2, ab, pre, ln, rows_per_image))
     return gemm_wxa8(None, None, M, ab, out_dtype, out=out, extra=extra, _fused_bytes=x2.element_size() * M * ab.pw.K)
 
@@ -746,6 +839,7 @@ def quant_linear(x: torch.Tensor, ab: ActBinding, pre_act=0, residual=None, fq=N
         res2 = residual.reshape(-1, ab.pw.N)
         if not res2.is_contiguous():
             res2 = res2.contiguous()
+    ab = _bind_rows(ab, x2, (rows, 1, 1, K, 1, 1, 1, 0), pre, ln)
     if pre_act != 2 and act_fuses(ab, rows, K, x.dtype, x2=x2):
         y = gemm_act(x2, rows, ab, x.dtype, extra=make_extra(res2, fq, geglu=geglu), pre=pre, ln=ln)
         return y.view(*x.shape[:-1], y.shape[-1])
@@ -787,6 +881,12 @@ def quant_linear_multi(x: torch.Tensor, bindings, ln=None):
         x2 = x2.contiguous()
     M = x2.shape[0]
     dev = x2.device
+    if any(ab.dynamic for ab in bindings):              # real-time layers of one input (and one bit width) share their row tables
+        tables = {}
+        for ab in bindings:
+            if ab.dynamic and ab.abits not in tables:
+                tables[ab.abits] = act_row_params(x2, (M, 1, 1, Kin, 1, 1, 1, 0), ab.abits, None, ln)
+        bindings = [ab.bound(*tables[ab.abits]) if ab.dynamic else ab for ab in bindings]
     outs = [torch.empty((M, ab.pw.N), dtype=x.dtype, device=dev) for ab in bindings]
     per_m = [0 if ab.mode == "perK" else 1 for ab in bindings]
     if _multi_fuses(bindings, M, Kin, x.dtype, x2):
@@ -868,6 +968,7 @@ def quant_conv2d(x: torch.Tensor, ab: ActBinding, kh, kw, stride, pad, norm=None
     xc = x.contiguous(memory_format=torch.channels_last)
     x_store = xc.permute(0, 2, 3, 1)                  # [B,H,W,C] view over the same storage, contiguous
     pre = (*_gn_input(x, x_store, norm), norm[4]) if norm is not None else None
+    ab = _bind_rows(ab, x_store, (B, H, W, C, kh, kw, stride, pad), pre, ups=upsample)      # (real-time: this operand's row tables)
     Ho = (H + 2 * pad - kh) // stride + 1
     Wo = (W + 2 * pad - kw) // stride + 1
     M = B * Ho * Wo

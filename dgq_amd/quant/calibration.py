@@ -68,6 +68,13 @@ def load_cali_model(qnn: QuantModel, init_data: Tuple[torch.Tensor], use_aq: boo
     """Same signature as the reference plus ``init_forward``: with ``False`` the data-dependent scalar
     self-initialisation forward of calibration.py:256-257 is skipped (quantizers not covered by the ckpt
     then initialise on their first real input) — used by CPU-side tests of the loader logic."""
+    # real-time activation quantizers (UniformAffineQuantizer(real_time=True), a mode of this library): the parameters come from every
+    # call's own rows, so no activation table is read (``act_*`` blocks of the file are ignored, ``use_group`` has nothing to
+    # regroup) and no dummy-batch initialisation runs; per-timestep tables and real-time parameters exclude each other
+    real_time = any(isinstance(m, QuantLayer) and m.aqtizer.real_time for m in qnn.model.modules())
+    if real_time and use_aq and time_aware_aqtizer:
+        raise ValueError("time_aware_aqtizer=True with real-time aq_params: per-timestep activation tables and real-time "
+                         "per-row parameters are exclusive")
     logger.info("Loading calibration model...")
     try:                                          # zip-format files are memory-mapped: pages are read as tensors are used
         full = torch.load(path, map_location="cpu", mmap=True)
@@ -96,7 +103,9 @@ def load_cali_model(qnn: QuantModel, init_data: Tuple[torch.Tensor], use_aq: boo
     logger.info("keys not loaded: %s", missing)
     qnn.set_quant_state(use_wq=True, use_aq=False)
 
-    if use_aq:
+    if use_aq and real_time:
+        qnn.set_quant_state(use_wq=True, use_aq=True)
+    elif use_aq:
         qnn.set_quant_state(use_wq=True, use_aq=True)
         if init_forward:
             dev = qnn.device

@@ -163,6 +163,16 @@ class QuantResnetBlock2D(BaseQuantBlock):
         return self._norm_act_conv(self.norm2, self.conv2, h, residual=sc, final=True)     # shortcut + conv2(...) in the epilogue
 
 
+def _qparams_real_time(specs):
+    """(mode 1, δ, z) of real-time attention-side quantizers for THIS call's projection outputs: one (δ, z) per token over batch and
+    heads — the rows b·T + t of the [B·T][H·D] tensor folded over b (dgq_act_row_params with fold_T = T), the (1, T, 1) layout with the
+    ``skip`` bypassed leading tokens dropped.  specs: [(tensor [B, T, H·D] contiguous, skip, bits)]; q, k and v of one attention share
+    the launches."""
+    tabs = ops.act_row_params_multi([(t, (t.shape[0] * t.shape[1], 1, 1, t.shape[2], 1, 1, 1, 0), bits, None, None, False, t.shape[1])
+                                     for t, _skip, bits in specs])
+    return [(1, d[skip:], z[skip:]) for (d, z), (_t, skip, _bits) in zip(tabs, specs)]
+
+
 def _qparams(q: UniformAffineQuantizer, dev):
     """(mode, δ, z) of an attention-side quantizer for dgq_fakequant_rows on the [B·T, H·D] layout:
     () -> scalar; (1,T,1) -> per token; (1,1,D) -> per head-dim (quant_layer.py:311-313, 391-402)."""
@@ -239,6 +249,7 @@ class QuantBasicTransformerBlock(BaseQuantBlock):
             attn.aqtizer_k = UniformAffineQuantizer(**aq_params)
             attn.aqtizer_v = UniformAffineQuantizer(**aq_params)
         aq_params_w = dict(aq_params)
+        aq_params_w.pop("real_time", None)                     # (the layer-side flag: aqtizer_w keeps t2i_log_quant / t2i_real_time)
         aq_params_w["bits"] = softmax_aq_params["softmax_a_bit"]
         aq_params_w["symmetric"] = False
         aq_params_w["always_zero"] = True
@@ -306,6 +317,7 @@ def quant_attention_forward(attn, hidden_states, encoder_hidden_states=None, res
              and D in ops.ATTN_HEAD_DIMS and (mode_w == 1 or attn.aqtizer_w.init)
              and ops.attention_fuses_fakequant(D, mode_w))
     pending = {}
+    pending_rt = {}                                                  # real-time quantizers: name -> (tensor, skip, bits), resolved together
 
     # projections that share their launches: q/k/v of a self-attention (same input, LayerNorm folded once per problem) ...
     pre = {}
@@ -333,17 +345,25 @@ def quant_attention_forward(attn, hidden_states, encoder_hidden_states=None, res
         ntok = inp.shape[1]
         if name in pre:
             ten = pre[name]
+            if defer and qz.real_time:
+                ten = ten.contiguous()
+                pending_rt[name] = (ten, skip, qz.bits)
+                return ten
             if defer and qz.init:
                 mode, dd, zz = _qparams(qz, ten.device)
                 pending[name] = (mode, dd, zz, skip, qz.bits)
                 return ten
             layer = lambda _x, _t=ten: _t                             # already projected: only the quantizer is left
             inp = ten
+        if defer and qz.real_time:
+            ten = _apply(layer, inp).contiguous()
+            pending_rt[name] = (ten, skip, qz.bits)
+            return ten
         if defer and qz.init:
             mode, dd, zz = _qparams(qz, inp.device)
             pending[name] = (mode, dd, zz, skip, qz.bits)
             return _apply(layer, inp)
-        if (FUSION and _F_FQ and qz is not None and qz.init and isinstance(layer, QuantLayer)
+        if (FUSION and _F_FQ and qz is not None and qz.init and not qz.real_time and isinstance(layer, QuantLayer)
                 and layer.on_integer_path(inp.x if isinstance(inp, PreLN) else inp) and inp.dtype in ops.FLOAT_DTYPES):
             mode, dd, zz = _qparams(qz, inp.device)
             return _apply(layer, inp, fq=(mode + 1, dd, zz, ntok, D, skip, qz.bits))
@@ -356,14 +376,18 @@ def quant_attention_forward(attn, hidden_states, encoder_hidden_states=None, res
             if qz.calibrating():                                     # DGQ calibration: the quantizer sees [B,H,T−skip,D]
                 view = ten.view(bb, ntok, H, D)
                 qz.observe((view[:, skip:] if skip else view).transpose(1, 2))
-            mode, dd, zz = _qparams(qz, ten.device)
             ten = ten.contiguous()
+            mode, dd, zz = _qparams_real_time([(ten, skip, qz.bits)])[0] if qz.real_time else _qparams(qz, ten.device)
             ops.fakequant_rows(ten.view(bb * ntok, cc), ntok, D, mode, dd, zz, skip, qz.bits)
         return ten
 
     q = project(attn.to_q, "aqtizer_q", hidden_states, 0)
     k = project(attn.to_k, "aqtizer_k", src, 1 if start_peak else 0)
     v = project(attn.to_v, "aqtizer_v", src, 0)
+    if pending_rt:                                                   # one dgq_act_row_params_batch call for q, k and v
+        names = list(pending_rt)
+        for nm, (mode, dd, zz) in zip(names, _qparams_real_time([pending_rt[nm] for nm in names])):
+            pending[nm] = (mode, dd, zz, pending_rt[nm][1], pending_rt[nm][2])
     b, t, c = q.shape
     s = k.shape[1]
     # weight reconstruction (reconstruction.py) differentiates through the block: the fused kernels have no backward, so a

@@ -154,6 +154,19 @@ def channel_minmax(w: torch.Tensor, level: int):
     return delta.view(shape), zp.view(shape)
 
 
+def row_minmax(row_min: torch.Tensor, row_max: torch.Tensor, level: int):
+    """``minmax`` of many rows at once from their fp32 minima / maxima — the statement dgq_act_row_params reproduces bit for bit (the
+    real-time activation quantizer): lo = min(row_min, 0), hi = max(row_max, 0), δ = fp32((double(hi) − double(lo)) / (level − 1)),
+    fp32(1e-8) when smaller, z = rne(fp32(−lo) / δ) with an fp32 IEEE division.  Equal to the scalar ``minmax`` of each row
+    (tests/test_realtime_act_cpu.py)."""
+    lo = torch.clamp(row_min.float(), max=0.0)
+    hi = torch.clamp(row_max.float(), min=0.0)
+    delta = ((hi.double() - lo.double()) / float(level - 1)).float()
+    delta = torch.where(delta < 1e-8, torch.full_like(delta, 1e-8), delta)
+    zp = torch.round(-lo / delta)
+    return delta, zp
+
+
 def group_params_from_ranges(in_min, in_max, out_min, out_max, group_num, mode, level, force_in_channel=None):
     """The host half of ``done_group_num`` (quant_layer.py:338-418) as a pure function of the folded range vectors —
     returns (δ, z, in_channel_wise) in the checkpoint's broadcast shapes.  Arithmetic follows the reference line by
@@ -198,14 +211,23 @@ def group_params_from_ranges(in_min, in_max, out_min, out_max, group_num, mode, 
 
 class UniformAffineQuantizer(nn.Module):
     """δ·(clamp(rne(x/δ)+z, 0, 2^b−1) − z)  — quant_layer.py:216-299 (inference branch; the calibration branches of
-    :284-293 are ``observe``)."""
+    :284-293 are ``observe``).
+
+    ``real_time=True`` (a mode of this library; the reference has it for the softmax quantizer only): no stored (δ, z) — every row
+    the quantizer sees gets its own pair from ``Scaler.MINMAX`` applied to that row at run time (dgq_act_row_params; ``row_minmax``
+    below is the statement).  The row of a Linear layer is a row of its [M][K] input, the row of a convolution one output position's
+    row of the unfolded operand, both behind any folded prologue; an attention-side quantizer (aqtizer_q/k/v) takes one pair per
+    token over batch and heads.  Needs no activation calibration; ``init_from`` is a no-op and the quantizer is always ``init``."""
 
     def __init__(self, bits: int = 8, symmetric: bool = False, channel_wise: bool = False,
                  scaler: Scaler = Scaler.MINMAX, leaf_param: bool = False, always_zero: bool = False,
-                 quant_emb: bool = False) -> None:
+                 quant_emb: bool = False, real_time: bool = False) -> None:
         super().__init__()
         if symmetric:
             raise NotImplementedError("symmetric quantizers are not used by the DGQ inference path")
+        if real_time and (channel_wise or always_zero or scaler is not Scaler.MINMAX):
+            raise ValueError("a real-time activation quantizer is Scaler.MINMAX per row: not channel_wise, not always_zero")
+        self.real_time = bool(real_time)
         self.level = 2 ** bits
         self.symmetric = symmetric
         self.channel_wise = channel_wise
@@ -217,7 +239,7 @@ class UniformAffineQuantizer(nn.Module):
         self.always_zero = always_zero
         self.delta = None
         self.zero_point = None
-        self.init = False
+        self.init = self.real_time                 # nothing to initialise: the parameters come from each call's rows
         self.quant_emb = quant_emb
         self.group_num = -1
         # calibration producer state (quant_layer.py:247-248): one (min, max) pair of vectors per observed batch
@@ -309,6 +331,8 @@ class UniformAffineQuantizer(nn.Module):
         return self.scaler(x, self.symmetric, self.level, self.always_zero)
 
     def init_from(self, x: torch.Tensor):
+        if self.real_time:
+            return
         delta, zp = self._init_quantization_param(x, self.channel_wise)
         self.delta = nn.Parameter(delta) if self.leaf_param else delta
         self.zero_point = zp
@@ -336,6 +360,17 @@ class UniformAffineQuantizer(nn.Module):
         if not x.is_cuda:
             raise RuntimeError("dgq_amd: quantizers execute on the GPU only (no CPU fallback)")
         xc = x.contiguous()
+        if self.real_time:
+            # stand-alone (fake-quant) form: the rows of the last dimension, their tables from dgq_act_row_params, then
+            # dgq_fakequant_rows with one table entry per row.  A convolution's rows exist only inside the layer (unfolded operand).
+            if x.dim() == 4 or x.shape[-1] % 4 != 0 or x.dtype not in ops.FLOAT_DTYPES:
+                raise NotImplementedError("stand-alone real-time quantizer: [..., C] inputs with C % 4 == 0 (a convolution's rows are "
+                                          "those of its unfolded operand: use the QuantLayer)")
+            x2d = xc.view(-1, x.shape[-1])
+            d, z = ops.act_row_params(x2d, (x2d.shape[0], 1, 1, x2d.shape[1], 1, 1, 1, 0), self.bits)
+            out = torch.empty_like(xc)
+            ops.fakequant_rows(x2d, x2d.shape[0], x2d.shape[1], 1, d, z, 0, self.bits, out=out.view(x2d.shape))
+            return out
         x2d, mode, T, D = self.layout(xc)
         d = self.delta.detach().reshape(-1).float().to(x.device)
         z = torch.as_tensor(self.zero_point).detach().reshape(-1).float().to(x.device)
@@ -349,8 +384,8 @@ class UniformAffineQuantizer(nn.Module):
         self.level = 2 ** bits
 
     def extra_repr(self) -> str:
-        return "level=%d, channel_wise=%s, leaf_param=%s, always_zero=%s" % (
-            self.level, self.channel_wise, self.leaf_param, self.always_zero)
+        return "level=%d, channel_wise=%s, leaf_param=%s, always_zero=%s%s" % (
+            self.level, self.channel_wise, self.leaf_param, self.always_zero, ", real_time=True" if self.real_time else "")
 
     def half(self):
         super().half()
@@ -471,7 +506,7 @@ class QuantLayer(nn.Module):
 
     def _has_act_table(self) -> bool:
         """the activation quantizer is initialised, or the live timestep slot has a table"""
-        return bool(self.aqtizer.init or (self._slot_ref is not None and self._slot_ref.slot in self._act_tables))
+        return bool(self.aqtizer.init or (self._slot_ref is not None and self._slot_ref.slot in self._act_tables))   # (real-time: always init)
 
     # -- weights ------------------------------------------------------------------------------------
     def _weight_key(self):
@@ -544,6 +579,10 @@ class QuantLayer(nn.Module):
 
     def _binding(self) -> ops.ActBinding:
         pw = self.packed_weight()
+        if self.aqtizer.real_time:                # no tables, no slots: one natural-order binding, its row tables made per call
+            if "real_time" not in self._bindings:
+                self._bindings["real_time"] = ops.DynamicActBinding(pw, self.aqtizer.bits)
+            return self._bindings["real_time"]
         slot = self._slot_ref.slot if self._slot_ref is not None else None
         if slot is not None and slot in self._act_tables:
             key = slot

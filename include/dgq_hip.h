@@ -42,7 +42,9 @@ extern "C" {
  *   121  round 6: dgq_cfg_ddim_step takes the tensors' dtype (void pointers + `dtype`); dgq_attention_workspace_bytes grew by one fp32
  *        part area (key-split launches on 16-bit tensors)
  *   122  round 6: dgq_gemm_extra_t += y2, ldy2; dgq_conv2d_f32w takes y2 / ldy2 / gn_partial
- *   123  dgq_conv2d_wq (the weight-only state from the packed W4 / W8 codes) */
+ *   123  dgq_conv2d_wq (the weight-only state from the packed W4 / W8 codes); later, without a new revision because no existing
+ *        entry or struct changed (a binding written against 123 keeps working): the real-time per-row activation quantiser tables,
+ *        dgq_act_row_params / dgq_act_row_params_batch with their dgq_act_rowparams_out_t */
 #define DGQ_ABI_VERSION 123
 int dgq_version(void);
 const char* dgq_last_error(void);
@@ -139,6 +141,28 @@ int dgq_quant_act_variant(const dgq_quant_act_args_t* args);
 /* tile id (1: 4x8, 2: 4x4, 3: 2x4 output positions; 0: the patch does not fit, no block-staged path) and patch width PW
  * = (TW − 1)·stride + kw of the block-staged conv path for a geometry: what the caller needs to build `kpat` */
 int dgq_quant_act_conv_tile(int C, int kh, int kw, int stride, int Kp, int* patch_w);
+
+/* ---- activations: real-time per-row quantiser tables (a mode of this library; the reference has no such layer quantiser) ----------
+ * One (δ, z) per row the activation quantiser sees, from Scaler.MINMAX applied to that row at run time: lo = min(row min, 0),
+ * hi = max(row max, 0), δ = fp32((double(hi) − double(lo)) / (2^bits − 1)), fp32(1e-8) when smaller, z = rne(fp32(−lo) / δ) (IEEE
+ * division) — bit for bit.  The row of a Linear layer is a row of its [M][C] input; the row of a convolution is one output
+ * position's row of the unfolded operand (C·kh·kw values, zeros outside the image — MINMAX includes 0 anyway).  Both AFTER the
+ * folded prologue, evaluated by the device functions of dgq_quant_act, so that the quantiser sees the same x′.
+ * `in` describes the input exactly as for dgq_quant_act: x, x_dtype, B, H, W, C, kh, kw, stride, pad, bits, pre_scale / pre_shift /
+ * pre_act, ln_gamma / ln_beta / ln_eps, ups are read (x 16-byte aligned, C % 4 == 0); its tables, Kp and outputs are ignored.
+ * delta_out / zp_out [M]: what the per-M routes take as mdelta / mzp with L = M (dgq_quant_act, dgq_gemm_wxa8 with or without
+ * quantise-on-load).
+ * fold_T > 0 (Linear inputs, fold_T | M): rows with equal r % fold_T share one pair — delta_out / zp_out [fold_T], the (1, T, 1) layout
+ * of the attention-side quantisers (dgq_attn_fq_t mode 1, dgq_fakequant_rows mode 1).
+ * ws: caller-owned scratch of 2 floats per input pixel (B·H·W, a quarter with ups), 8-byte aligned — needed by convolutions (anything
+ * but 1x1 / stride 1 / pad 0) and by fold_T > 0; one launch otherwise, two with it.  No allocation, no synchronisation, no atomics:
+ * capture-safe.  The batch form takes 1..4 problems of one dtype that are all of the two-launch kind or all of the one-launch kind
+ * (the q / k / v outputs of an attention, any row counts) and shares the launches. */
+typedef struct dgq_act_rowparams_out {
+    int fold_T; float* ws; size_t ws_floats; float* delta; float* zp;
+} dgq_act_rowparams_out_t;
+int dgq_act_row_params(const dgq_quant_act_args_t* in, int fold_T, float* ws, size_t ws_floats, float* delta_out, float* zp_out, void* stream);
+int dgq_act_row_params_batch(int n, const dgq_quant_act_args_t* in, const dgq_act_rowparams_out_t* out, void* stream);
 
 /* GroupNorm of a channels-last tensor x [B][HW][C] as per-(b,c) scale/shift (biased variance, eps as F.group_norm):
  * GN(x) = x·scale + shift.  Replaces norm1/norm2 of QuantResnetBlock2D.forward (quant_block.py:98-119) together with

@@ -1,0 +1,193 @@
+#!/usr/bin/env python3
+"""Measures the real-time per-row activation mode (UniformAffineQuantizer(real_time=True), dgq_act_row_params) against the calibrated
+c2 tables, same box, same process — profiles/r08_realtime_act.txt:
+
+  * the SD-size synthetic model, CFG pair, fp32: ms per step (hipGraph replay, median of the windows), library launches per step
+    (entry calls of one eager step), model_ready seconds, device memory after load — calibrated c2 (time-aware g16 tables) and
+    real-time (weight-only checkpoint);
+  * the row-parameter kernels alone, replayed from a hipGraph: µs and input bytes / time at four SD shapes.
+
+    python tools/profile_realtime_act.py --out profiles/r08_realtime_act.txt --stamp "$(git rev-parse --short HEAD)"
+"""
+import argparse
+import gc
+import os
+import statistics
+import subprocess
+import sys
+import time
+import types
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def stamp_default():
+    try:
+        return subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], stderr=subprocess.DEVNULL).decode().strip()
+    except Exception:
+        return "unknown"
+
+
+def replayed_us(torch, issue, rep=20, rounds=5):
+    """median µs of one ``issue()`` out of ``rep`` back-to-back calls replayed from a hipGraph (launch gaps of eager calls excluded)"""
+    issue()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(rep):
+            issue()
+    g.replay()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(rounds):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        g.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1) * 1e3 / rep)
+    return statistics.median(out)
+
+
+def kernel_table(torch, ops, dev, lines):
+    lines.append("row-parameter kernels alone (fp32 input, A8; %d calls per hipGraph replay, median of 5 replays)" % 20)
+    lines.append("%-28s %8s %10s %12s %9s" % ("shape", "launches", "us / call", "input MB", "GB/s"))
+    g = torch.Generator().manual_seed(0)
+    shapes = [("linear 8192 x 320", (8192, 1, 1, 320, 1, 1, 1, 0)), ("linear 8192 x 1280", (8192, 1, 1, 1280, 1, 1, 1, 0)),
+              ("conv 2x320x64x64 k3", (2, 64, 64, 320, 3, 3, 1, 1)), ("conv 2x1280x16x16 k3", (2, 16, 16, 1280, 3, 3, 1, 1))]
+    for name, geom in shapes:
+        B, H, W, C = geom[:4]
+        x = torch.randn(B, H, W, C, generator=g).to(dev)
+        us = replayed_us(torch, lambda: ops.act_row_params(x, geom, 8))
+        nbytes = x.numel() * 4
+        lines.append("%-28s %8d %10.2f %12.2f %9.0f" % (name, 1 if geom[4:] == (1, 1, 1, 0) else 2, us, nbytes / 1e6, nbytes / us / 1e3))
+
+
+def build_model(torch, mode, steps_cfg, slots, batch, dev):
+    """(qnn, seconds until ready, GB allocated on the device once ready)"""
+    import bench
+    from dgq_amd import synth
+    from dgq_amd.runtime import build_synthetic_qnn, quant_params
+    gc.collect()
+    torch.cuda.empty_cache()
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    t0 = time.perf_counter()
+    cfg = dict(bench.CONFIGS["c2"]["cfg"])
+    if mode == "calibrated":
+        bench.write_synthetic_ckpt("sd", cfg, 64, batch, max(slots) + 1)
+        qnn, _ = build_synthetic_qnn("sd", cfg, 64, batch, max(slots) + 1, device=dev)
+        qnn.prepare_slots(slots)
+    else:
+        from dgq_amd.diffusers_rewrite import UNet2DConditionModel
+        from dgq_amd.quant import get_qmodel, Scaler
+        path = "/tmp/dgq_synth_sd_w4_weight_only.pth"
+        if not os.path.exists(path):
+            synth.write_cali_ckpt(path, "sd", 4, 8, 1, num_slots=1, seed=0, batch=batch, res=64, with_act=False)
+        unet = UNet2DConditionModel("sd")
+        unet.load_state_dict(synth.state_dict_from_ckpt(path))
+        wq, aq, sm = quant_params(Scaler, 4, 8, True, cfg["log"], cfg["rt"], cfg["sp"])
+        aq["real_time"] = True
+        qnn = get_qmodel("sd", types.SimpleNamespace(unet=unet), path, wq, True, aq, sm, False, steps_cfg, False, device=dev)
+        qnn = qnn.float().to(dev)
+        qnn.disable_out_quantization()
+    torch.cuda.synchronize()
+    ready = time.perf_counter() - t0
+    return qnn, ready, (torch.cuda.memory_allocated() - base) / 1e9
+
+
+def time_model(torch, ops, qnn, timesteps, warmup, windows, dev):
+    from dgq_amd import synth
+    from dgq_amd.runtime import DDIMScheduler
+    sch = DDIMScheduler(50)
+    lat = synth.named_randn("latent", (1, 4, 64, 64), 1).to(dev)
+    ctx = synth.named_randn("ctx", (2, 77, 768), 100).to(dev)
+
+    def one_step(x, t):
+        eps = qnn(torch.cat([x, x], dim=0), t, ctx)[0]
+        return sch.step_guided(eps, t, x, 7.5) if hasattr(sch, "step_guided") else sch.step(eps.chunk(2)[0] + 7.5 * (eps.chunk(2)[1] - eps.chunk(2)[0]), t, x)
+
+    calls = []
+    orig = ops._lib_call
+    with torch.no_grad():
+        one_step(lat, timesteps[0])                          # lazy initialisations, eager
+        ops._lib_call = lambda name, *a: (calls.append(name), orig(name, *a))[1]
+        try:
+            one_step(lat, timesteps[0])
+        finally:
+            ops._lib_call = orig
+        torch.cuda.synchronize()
+        after_step = torch.cuda.memory_allocated() / 1e9
+        qnn.enable_graphs(True)
+        for t in sorted(set(timesteps), reverse=True):
+            one_step(lat, t)
+        x = lat
+        for t in timesteps[:warmup]:
+            x = one_step(x, t)
+        xw, secs = x, []
+        for _ in range(windows):
+            x = xw
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for t in timesteps[warmup:]:
+                x = one_step(x, t)
+            torch.cuda.synchronize()
+            secs.append((time.perf_counter() - t0) / len(timesteps[warmup:]))
+        assert torch.isfinite(x).all()
+        qnn.enable_graphs(False)
+    by = {}
+    for n in calls:
+        by[n] = by.get(n, 0) + 1
+    return statistics.median(secs) * 1e3, len(calls), by, after_step
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--out", default="profiles/r08_realtime_act.txt")
+    ap.add_argument("--stamp", default=None, help="commit the tree was built from (default: git rev-parse)")
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--windows", type=int, default=3)
+    ap.add_argument("--kernels-only", action="store_true")
+    args = ap.parse_args(argv)
+    import torch
+    from dgq_amd import _lib, ops
+    from dgq_amd.runtime import DDIMScheduler
+    _lib.require_gpu()
+    torch.set_num_threads(min(torch.get_num_threads(), 16))
+    dev = torch.device("cuda", 0)
+    lines = ["real-time per-row activation mode vs calibrated c2 tables — tools/profile_realtime_act.py",
+             "commit %s; %s; torch %s; ABI %d" % (args.stamp or stamp_default(), torch.cuda.get_device_name(0), torch.__version__, _lib.ABI_VERSION), ""]
+    kernel_table(torch, ops, dev, lines)
+    if not args.kernels_only:
+        sched = DDIMScheduler(50).timesteps
+        n = args.steps + args.warmup
+        timesteps = [int(sched[i % min(n, len(sched))]) for i in range(n)]
+        slots = sorted({(1000 - t) // 20 for t in timesteps})
+        lines += ["", "SD1.4-size synthetic model, 512^2 (64x64 latents), CFG pair, fp32, W4A8; %d timed steps x %d windows behind %d warm-up steps, hipGraph replay"
+                  % (args.steps, args.windows, args.warmup),
+                  "%-38s %10s %12s %14s %14s %14s" % ("mode", "ms / step", "launches", "model_ready s", "GB after load", "GB after step")]
+        detail = []
+        for mode, label in (("calibrated", "calibrated c2 (g16, %d time-aware slots)" % len(slots)), ("real_time", "real-time rows (weight-only ckpt)")):
+            qnn, ready, gb = build_model(torch, mode, 50, slots, 2, dev)
+            ms, ncalls, by, gb_step = time_model(torch, ops, qnn, timesteps, args.warmup, args.windows, dev)
+            lines.append("%-38s %10.3f %12d %14.1f %14.2f %14.2f" % (label, ms, ncalls, ready, gb, gb_step))
+            detail.append("%s: %s" % (mode, ", ".join("%s %d" % kv for kv in sorted(by.items(), key=lambda kv: -kv[1]))))
+            del qnn
+            ops._WORKSPACE.clear()
+            gc.collect()
+            torch.cuda.empty_cache()
+        lines += ["", "launches = entry calls of libdgq_hip.so in one eager step (a call is one to three kernel launches), by entry:"] + detail
+        lines += ["", "GB = torch.cuda.memory_allocated() growth over the build (weights, packed images, tables; the calibrated figure counts the",
+                  "slots this run visits, not all 25 / 50 of a full schedule); model_ready includes writing the synthetic checkpoint when /tmp has none."]
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+    print(text)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
