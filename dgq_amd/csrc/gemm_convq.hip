@@ -16,7 +16,7 @@
 //   3. run the slab's K tiles of gemm_panel_kernel's loop: A fragments from LDS, int4 weights streamed fragment-major into registers
 //      (hand-counted waits; the stream runs on across the slab switches), per-K group flushes by summation by parts;
 //   4. the dequantising store epilogue of the family (gemm_tile.h, TILED row mapping: residual / temb rows / GroupNorm partials).
-// No code matrix, no row-sum vector, one launch instead of two.  LDS (C = 320, Kp = 3072): patch 75 KB + tables 7 KB + slab 40 KB +
+// No code matrix, no row-sum vector, one launch instead of two.  LDS (C = 320, Kp = 3072): patch 75 KB + tables 8 KB + slab 40 KB +
 // epilogue vectors 6 KB.  Layers it takes (dgq_gemm_conv_act_fuses): 3x3, stride 1, pad 1, W4, N % 32 == 0 and N <= 320, H % 4 == 0,
 // W % 8 == 0, patch + tables + a 10-tile slab within 160 KB (C <= 340) — the C = 320 convolutions of the 64 x 64 level of SD.  Layers with
 // more input channels (the concatenated up-path inputs, the 32 x 32 level) keep the two-launch form: their patch alone exceeds the LDS.
@@ -46,7 +46,7 @@ __host__ __device__ inline ConvqLds convq_lds(int C, int kh, int kw, int stride,
     l.patch = 0;
     l.tab = cq_align16(patch > ep ? patch : ep);
     l.tdl = l.tab + cq_align16(Kp * 2);
-    l.rowt = l.tdl + cq_align16((Kp >> 5) * 8);
+    l.rowt = l.tdl + cq_align16(dgq_conv_rec_bytes(Kp));   // the per-chunk records (quant_common.h)
     l.slab = l.rowt + 3 * 32 * 4;
     l.vtab = l.slab + slab_tiles * 32 * BK;
     l.total = l.vtab + (3 * 32 + 4 * 32 * nw) * 4 + (per_m ? 0 : cq_align16((NCH + 1) * (Kp / BK) * 4));
@@ -194,21 +194,17 @@ __global__ __launch_bounds__(64 * NW) void gemm_convq_kernel(GemmBatch bt, int s
         }
     }
     DGQ_STAMP(3);                                          // (diagnostic) patch staged
-    // the gather table, the chunks' (δ, z) and the rows' (δ, z, 1/δ) into LDS
+    // the gather table and the chunks' records, resolved once per workgroup (quant_common.h), and the rows' (δ, z, 1/δ) into LDS
     uint16_t* tab = reinterpret_cast<uint16_t*>(smem + L.tab);
-    float* tdl = reinterpret_cast<float*>(smem + L.tdl);
-    float* tzp = tdl + (p.Kp >> 5);
+    DgqChunkRec* rec = reinterpret_cast<DgqChunkRec*>(smem + L.tdl);
     float* rowt = reinterpret_cast<float*>(smem + L.rowt);     // per-M: [3][32] δ, z, 1/δ of the tile's rows
-    for (int k = tid * 4; k < p.Kp; k += 4 * NT) {
-        const int4 e = *reinterpret_cast<const int4*>(act.kpat + k);
-        *reinterpret_cast<uint2*>(tab + k) = make_uint2(((uint32_t)e.x & 0xFFFFu) | ((uint32_t)e.y << 16), ((uint32_t)e.z & 0xFFFFu) | ((uint32_t)e.w << 16));
-    }
-    if constexpr (!PER_M) {
-        for (int c = tid; c < (p.Kp >> 5); c += NT) { tdl[c] = p.cdelta[c]; tzp[c] = act.czp[c]; }
-    } else if (tid < 32) {
-        const int li = (m0 + (tid >> 3) * Wo + (tid & 7)) % p.L;
-        const float md = p.mdelta[li];
-        rowt[tid] = md; rowt[32 + tid] = p.mzp[li]; rowt[64 + tid] = dgq_rcp(md);
+    dgq_conv_tables_resolve<PER_M>(act.kpat, p.cdelta, act.czp, p.Kp, tab, rec, tid, NT);
+    if constexpr (PER_M) {
+        if (tid < 32) {
+            const int li = (m0 + (tid >> 3) * Wo + (tid & 7)) % p.L;
+            const float md = p.mdelta[li];
+            rowt[tid] = md; rowt[32 + tid] = p.mzp[li]; rowt[64 + tid] = dgq_rcp(md);
+        }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the first W tiles and the tables
     if (PER_M) asm volatile("" : "+v"(c_al), "+v"(c_zw), "+v"(c_ga), "+v"(c_vn));
@@ -298,7 +294,9 @@ __global__ __launch_bounds__(64 * NW) void gemm_convq_kernel(GemmBatch bt, int s
     float partial[RQ];
 #pragma unroll
     for (int q = 0; q < RQ; ++q) partial[q] = 0.0f;
-    const float qmax = (float)((1 << act.bits) - 1), bias = 128.0f - p.offset;
+    const float qmax = (float)((1 << act.bits) - 1);
+    const uint32_t bias4 = (uint32_t)(int)(128.0f - p.offset) * 0x01010101u;
+    const uint32_t sh4 = 4u * (lane & 7);
     auto quantise_slab = [&](int k0, int k1) {
 #pragma unroll
         for (int q = 0; q < RQ; ++q) {
@@ -309,51 +307,21 @@ __global__ __launch_bounds__(64 * NW) void gemm_convq_kernel(GemmBatch bt, int s
             float md = 1.0f, mz = 0.0f, minv = 1.0f;
             if (PER_M) { md = rowt[r]; mz = rowt[32 + r]; minv = rowt[64 + r]; }
             const uint32_t row_base = (uint32_t)(r * BK), row_swz = (uint32_t)(((r >> 1) & 7) << 4);
+            auto store = [&](int kp0, uint32_t w) {
+                const int ks = kp0 - k0;                     // position inside the slab image
+                *reinterpret_cast<uint32_t*>(slab + (ks >> 7) * (BM * BK) + row_base + ((((uint32_t)ks & 127u) & ~15u) ^ row_swz) + (ks & 15)) = w;
+            };
             float part = partial[q];
             // QU = 5 steps of 256 codes per round: a 10-tile slab (1280 codes) is ONE round — every table read and every gather of the row's
             // slab in flight together.  (The lane -> code mapping and each lane's ascending order are quant_act_conv_kernel's, whose rounds
-            // are 4 steps: the row sums add up in the same order.)
+            // are 4 steps: the row sums add up in the same order.)  Whole rounds test no position; the last round of the last slab is
+            // the guarded form (wave-uniform skips, and the upper half-wave of a last half step when Kp is an odd multiple of 128).
             constexpr int QU = 5;
-            // (every condition of the round is wave-uniform — a step of 256 codes lies inside the slab as a whole, but for the upper half
-            // of the last step when Kp is an odd multiple of 128: those lanes compute on a clamped position and write nothing — so the
-            // compiler emits scalar branches, not exec-mask regions)
-            for (int kbu = k0; kbu < k1; kbu += 256 * QU) {   // wave-uniform round base
-                int idx[QU][4];
-#pragma unroll
-                for (int u = 0; u < QU; ++u) {
-                    const int kpc = min(kbu + 256 * u + lane * 4, p.Kp - 4);          // (clamped: a step past the slab reads, computes, discards)
-                    const uint2 tt = *reinterpret_cast<const uint2*>(tab + kpc);
-                    idx[u][0] = tt.x & 0xFFFF; idx[u][1] = tt.x >> 16; idx[u][2] = tt.y & 0xFFFF; idx[u][3] = tt.y >> 16;
-                }
-                float v[QU][4];
-#pragma unroll
-                for (int u = 0; u < QU; ++u)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[u][e] = pr[idx[u][e] == 0xFFFF ? 0 : idx[u][e]];   // padding reads element 0: value unused
-#pragma unroll
-                for (int u = 0; u < QU; ++u) {
-                    const int ku = kbu + 256 * u;             // wave-uniform
-                    if (ku >= k1) break;
-                    const int kp0 = ku + lane * 4;
-                    const bool in = kp0 < k1;                 // false only in the upper half-wave of a last half step
-                    const int kpc = min(kp0, p.Kp - 4);
-                    float d = md, z = mz, inv = minv;
-                    if (!PER_M) {
-                        d = tdl[kpc >> 5];
-                        z = tzp[kpc >> 5];
-                        inv = dgq_rcp(d);
-                    }
-                    float biased[4], qv[4], fsum = 0.0f;
-                    dgq_affine_code4_fast(v[u], d, inv, z, qmax, qv);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) biased[e] = idx[u][e] != 0xFFFF ? qv[e] + bias : 128.0f;
-                    const uint32_t w = dgq_pack4(biased, fsum);
-                    const int ks = kpc - k0;                  // position inside the slab image
-                    if (in) *reinterpret_cast<uint32_t*>(slab + (ks >> 7) * (BM * BK) + row_base + ((((uint32_t)ks & 127u) & ~15u) ^ row_swz) + (ks & 15)) = w;
-                    fsum -= 512.0f;
-                    part += in ? (PER_M ? fsum : d * fsum) : 0.0f;
-                }
-            }
+            int kbu = k0;                                    // wave-uniform round base
+            for (; kbu + 256 * QU <= k1; kbu += 256 * QU)
+                part = dgq_conv_quant_round<PER_M, QU, true>(pr, tab, rec, kbu, k1, lane, sh4, md, mz, minv, qmax, bias4, part, store);
+            if (kbu < k1)
+                part = dgq_conv_quant_round<PER_M, QU, false>(pr, tab, rec, kbu, k1, lane, sh4, md, mz, minv, qmax, bias4, part, store);
             partial[q] = part;
         }
     };

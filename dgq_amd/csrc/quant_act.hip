@@ -576,18 +576,12 @@ __global__ __launch_bounds__(64 * NW) void quant_act_conv_kernel(QuantActBatch b
             *reinterpret_cast<float4*>(dst + c) = make_float4(v[0], v[1], v[2], v[3]);
         }
     }
-    // the gather table (and the per-chunk quantiser tables) behind the patch: read once per workgroup, every row of the tile
-    // then finds them at LDS latency (read from L1 per row, their ~1 us round trips were exposed at two waves per SIMD)
-    // (16-bit entries: a patch holds < 2^16 floats; 0xFFFF = padding)
+    // the gather table and the per-chunk quantiser records behind the patch, resolved once per workgroup (quant_common.h): every row of
+    // the tile then finds them at LDS latency (read from L1 per row, their ~1 us round trips were exposed at two waves per SIMD)
+    // (16-bit entries: a patch holds < 2^16 floats)
     uint16_t* tab = reinterpret_cast<uint16_t*>(patch + PH * PW * p.C);
-    float* tdl = reinterpret_cast<float*>(tab + p.Kp);
-    float* tzp = tdl + (p.Kp >> 5);
-    for (int k = tid * 4; k < p.Kp; k += 4 * 64 * NW) {
-        const int4 e = *reinterpret_cast<const int4*>(p.kpat + k);
-        *reinterpret_cast<uint2*>(tab + k) = make_uint2(((uint32_t)e.x & 0xFFFFu) | ((uint32_t)e.y << 16), ((uint32_t)e.z & 0xFFFFu) | ((uint32_t)e.w << 16));
-    }
-    if (!PER_M)
-        for (int c = tid; c < (p.Kp >> 5); c += 64 * NW) { tdl[c] = p.delta[c]; tzp[c] = p.zp[c]; }
+    DgqChunkRec* rec = reinterpret_cast<DgqChunkRec*>(tab + p.Kp);
+    dgq_conv_tables_resolve<PER_M>(p.kpat, p.delta, p.zp, p.Kp, tab, rec, tid, 64 * NW);
     __syncthreads();
     // ---- gather + quantise: wave w takes output positions w, w + NW, ... of the tile; with more waves than positions (WPR waves per
     // position) a position's 1024-code steps are dealt round-robin over its waves and the row sum is the sum of their parts in wave order
@@ -595,7 +589,8 @@ __global__ __launch_bounds__(64 * NW) void quant_act_conv_kernel(QuantActBatch b
     static_assert(WPR == 1 || NW == WPR * TH * TW, "waves per position: a whole number");
     __shared__ float rs_part[WPR > 1 ? TH * TW * WPR : 1];
     const int part = WPR > 1 ? wv % WPR : 0;
-    const float bias = 128.0f - p.offset;
+    const uint32_t bias4 = (uint32_t)(int)(128.0f - p.offset) * 0x01010101u;
+    const uint32_t sh4 = 4u * (lane & 7);
     for (int r = wv / WPR; r < TH * TW; r += NW / WPR) {
         const int i = r / TW, j = r - i * TW;
         const int ho = ho0 + i, wo = wo0 + j;
@@ -612,40 +607,15 @@ __global__ __launch_bounds__(64 * NW) void quant_act_conv_kernel(QuantActBatch b
         }
         float partial = 0.0f;
         uint32_t* out = reinterpret_cast<uint32_t*>(p.codes + (int64_t)row * p.Kp);
-        for (int kb = lane * 4 + 1024 * part; kb < (live ? p.Kp : 0); kb += 1024 * WPR) {
-            int idx[4][4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int kp0 = kb + 256 * u;
-                uint2 tt = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
-                if (kp0 < p.Kp) tt = *reinterpret_cast<const uint2*>(tab + kp0);
-                idx[u][0] = tt.x & 0xFFFF; idx[u][1] = tt.x >> 16; idx[u][2] = tt.y & 0xFFFF; idx[u][3] = tt.y >> 16;
-            }
-            float v[4][4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) v[u][q] = pr[idx[u][q] == 0xFFFF ? 0 : idx[u][q]];   // padding reads element 0: value unused
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int kp0 = kb + 256 * u;
-                if (kp0 < p.Kp) {
-                    float d = md, z = mz, inv = minv;
-                    if (!PER_M) {
-                        d = tdl[kp0 >> 5];
-                        z = tzp[kp0 >> 5];
-                        inv = dgq_rcp(d);
-                    }
-                    float biased[4], qv[4], fsum = 0.0f;
-                    dgq_affine_code4_fast(v[u], d, inv, z, p.qmax, qv);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) biased[q] = idx[u][q] != 0xFFFF ? qv[q] + bias : 128.0f;
-                    out[kp0 >> 2] = dgq_pack4(biased, fsum);
-                    fsum -= 512.0f;
-                    partial += PER_M ? fsum : d * fsum;
-                }
-            }
-        }
+        auto store = [&](int kp0, uint32_t w) { out[kp0 >> 2] = w; };
+        // rounds of 4 steps (1024 codes), wave-uniform base; whole rounds test no position, the row's last round (Kp is a multiple of
+        // 128, not of 1024) is the guarded form
+        const int kend = live ? p.Kp : 0;
+        int kbu = 1024 * part;
+        for (; kbu + 1024 <= kend; kbu += 1024 * WPR)
+            partial = dgq_conv_quant_round<PER_M, 4, true>(pr, tab, rec, kbu, kend, lane, sh4, md, mz, minv, p.qmax, bias4, partial, store);
+        if (kbu < kend)
+            partial = dgq_conv_quant_round<PER_M, 4, false>(pr, tab, rec, kbu, kend, lane, sh4, md, mz, minv, p.qmax, bias4, partial, store);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) partial += __shfl_down(partial, o, 64);
         if constexpr (WPR == 1) {
@@ -697,6 +667,11 @@ static ConvTile conv_tile_geo(const QuantActParams& p) {
     }
     return t;
 }
+// The tile rule above is the one the layers were tuned (and their row-sum orders fixed) with: 8 bytes of tables per 32-chunk.  The
+// resolved records (quant_common.h) take 16; the launch asks for the difference on top, so that no geometry changes its tile.  (A
+// patch of >= kh·kw·C floats beside 2·Kp bytes of indices within 150 KB bounds the sum well below the 160 KB of a CU.)
+#define DGQ_QA_CONV_LDS_MAX (160 * 1024 - 256)            // the CU's LDS less the kernel's static row-sum parts
+static size_t conv_lds_bytes(const ConvTile& t, int Kp) { return t.lds + (size_t)(Kp >> 5) * (sizeof(DgqChunkRec) - 8); }
 static bool conv_block_pays(const QuantActParams& p, const ConvTile& t) {
     if (t.id == 0) return false;
     return conv_tiles(p, t) >= 256 && p.M >= 2048;
@@ -766,34 +741,36 @@ static void launch_quant_act(const QuantActBatch& bt, int n, int variant, bool p
     if (variant == 5) {
         const ConvTile t = conv_tile_geo(p0);
         const int tiles = p0.B * ((p0.Ho + t.th - 1) / t.th) * ((p0.Wo + t.tw - 1) / t.tw);
+        size_t lds5 = 0;
+        for (int i = 0; i < n; ++i) lds5 = std::max(lds5, conv_lds_bytes(t, bt.p[i].Kp));
         static std::atomic<bool> attr5[64];
         int dev = 0;
         (void)hipGetDevice(&dev);
         if (dev < 0 || dev >= 64 || !attr5[dev].load(std::memory_order_acquire)) {          // all six instantiations of this dtype, once
 #define DGQ_QA_ATTR(PM, TH_, TW_) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_act_conv_kernel<TIn, PM, TH_, TW_, 8>), \
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024)
+                                                            hipFuncAttributeMaxDynamicSharedMemorySize, DGQ_QA_CONV_LDS_MAX)
             DGQ_QA_ATTR(true, 4, 8); DGQ_QA_ATTR(false, 4, 8);
 #undef DGQ_QA_ATTR
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_act_conv_kernel<TIn, true, 4, 4, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_act_conv_kernel<TIn, false, 4, 4, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_act_conv_kernel<TIn, true, 2, 4, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_act_conv_kernel<TIn, false, 2, 4, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_act_conv_kernel<TIn, true, 4, 4, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, DGQ_QA_CONV_LDS_MAX);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_act_conv_kernel<TIn, false, 4, 4, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, DGQ_QA_CONV_LDS_MAX);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_act_conv_kernel<TIn, true, 2, 4, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, DGQ_QA_CONV_LDS_MAX);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_act_conv_kernel<TIn, false, 2, 4, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, DGQ_QA_CONV_LDS_MAX);
             if (dev >= 0 && dev < 64) attr5[dev].store(true, std::memory_order_release);
         }
-#define DGQ_QA_CONV(PM, TH_, TW_) hipLaunchKernelGGL((quant_act_conv_kernel<TIn, PM, TH_, TW_, 8>), dim3(tiles, 1, n), dim3(512), t.lds, st, bt)
+#define DGQ_QA_CONV(PM, TH_, TW_) hipLaunchKernelGGL((quant_act_conv_kernel<TIn, PM, TH_, TW_, 8>), dim3(tiles, 1, n), dim3(512), lds5, st, bt)
         if (t.id == 1) { if (per_m) DGQ_QA_CONV(true, 4, 8); else DGQ_QA_CONV(false, 4, 8); }
         else if (t.id == 2) {
             // 16 positions per tile: one wave per output position (16 waves) instead of two positions per wave — the gather / quantise phase is a
             // chain of dependent LDS reads per 1024 codes, and twice the waves hide twice the latency (same lanes, same order per row:
             // bit-identical; step +0.3-0.5 % same box)
-            if (per_m) hipLaunchKernelGGL((quant_act_conv_kernel<TIn, true, 4, 4, 16>), dim3(tiles, 1, n), dim3(1024), t.lds, st, bt);
-            else hipLaunchKernelGGL((quant_act_conv_kernel<TIn, false, 4, 4, 16>), dim3(tiles, 1, n), dim3(1024), t.lds, st, bt);
+            if (per_m) hipLaunchKernelGGL((quant_act_conv_kernel<TIn, true, 4, 4, 16>), dim3(tiles, 1, n), dim3(1024), lds5, st, bt);
+            else hipLaunchKernelGGL((quant_act_conv_kernel<TIn, false, 4, 4, 16>), dim3(tiles, 1, n), dim3(1024), lds5, st, bt);
         }
         else {
             // 8 positions per tile, 16 waves: two waves per position (the per-K row sum then adds its two parts: last-bit differences
             // against the one-wave order; per-M sums are exact integers)
-            if (per_m) hipLaunchKernelGGL((quant_act_conv_kernel<TIn, true, 2, 4, 16>), dim3(tiles, 1, n), dim3(1024), t.lds, st, bt);
-            else hipLaunchKernelGGL((quant_act_conv_kernel<TIn, false, 2, 4, 16>), dim3(tiles, 1, n), dim3(1024), t.lds, st, bt);
+            if (per_m) hipLaunchKernelGGL((quant_act_conv_kernel<TIn, true, 2, 4, 16>), dim3(tiles, 1, n), dim3(1024), lds5, st, bt);
+            else hipLaunchKernelGGL((quant_act_conv_kernel<TIn, false, 2, 4, 16>), dim3(tiles, 1, n), dim3(1024), lds5, st, bt);
         }
 #undef DGQ_QA_CONV
         return;
