@@ -677,21 +677,17 @@ static int launch_attn3(AttnParams p, const void* q_raw, unsigned char* planes, 
     static_assert(stats_lds <= 160 * 1024 && pv_lds <= 160 * 1024 && stats2_lds <= 160 * 1024 && pv2_lds <= 160 * 1024, "LDS ring too large");
     // up to 138 KB of dynamic LDS (D = 160): opt in, once per device (the attribute is per device)
     static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn3_stats_kernel<D, 4, QM>), hipFuncAttributeMaxDynamicSharedMemorySize, stats_lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn3_pv_kernel<D, true, 4, QM, VINT>), hipFuncAttributeMaxDynamicSharedMemorySize, pv_lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn3_pv_kernel<D, false, 4, QM, VINT>), hipFuncAttributeMaxDynamicSharedMemorySize, pv_lds);
-        if constexpr (D <= 64) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn3_stats_kernel<D, 8, QM>), hipFuncAttributeMaxDynamicSharedMemorySize, stats_lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn3_stats_kernel<D, 8, QM, TPS_S>), hipFuncAttributeMaxDynamicSharedMemorySize, stats2_lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn3_pv_kernel<D, true, 8, QM, VINT>), hipFuncAttributeMaxDynamicSharedMemorySize, pv_lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn3_pv_kernel<D, false, 8, QM, VINT>), hipFuncAttributeMaxDynamicSharedMemorySize, pv_lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn3_pv_kernel<D, true, 8, QM, VINT, TPS_P>), hipFuncAttributeMaxDynamicSharedMemorySize, pv2_lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn3_pv_kernel<D, false, 8, QM, VINT, TPS_P>), hipFuncAttributeMaxDynamicSharedMemorySize, pv2_lds);
-        }
-        if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
+    dgq_allow_dynamic_lds(attr_set, {{&attn3_stats_kernel<D, 4, QM>, stats_lds},
+                                     {&attn3_pv_kernel<D, true, 4, QM, VINT>, pv_lds},
+                                     {&attn3_pv_kernel<D, false, 4, QM, VINT>, pv_lds}});
+    if constexpr (D <= 64) {
+        static std::atomic<bool> attr_wide[64];
+        dgq_allow_dynamic_lds(attr_wide, {{&attn3_stats_kernel<D, 8, QM>, stats_lds},
+                                          {&attn3_stats_kernel<D, 8, QM, TPS_S>, stats2_lds},
+                                          {&attn3_pv_kernel<D, true, 8, QM, VINT>, pv_lds},
+                                          {&attn3_pv_kernel<D, false, 8, QM, VINT>, pv_lds},
+                                          {&attn3_pv_kernel<D, true, 8, QM, VINT, TPS_P>, pv2_lds},
+                                          {&attn3_pv_kernel<D, false, 8, QM, VINT, TPS_P>, pv2_lds}});
     }
     // the main kernels read fp32 queries: the caller's tensor when it is fp32 and aqtizer_q is not fused, else a scratch
     // copy (converted / fake-quantised) written by extra blocks of the pre-pass; QI8: int8 codes + per-query table

@@ -422,10 +422,8 @@ __device__ __forceinline__ v16f score_tile_q1(const unsigned short* kb, const bf
 __device__ __forceinline__ void attn_block_coords(int xcd_remap, int& bx, int& bh) {
     bx = blockIdx.x; bh = blockIdx.y;
     if (xcd_remap) {
-        const int gx = gridDim.x, T = gridDim.x * gridDim.y;
-        const int bid = blockIdx.x + gx * blockIdx.y;
-        const int q = T >> 3, r = T & 7, xcd = bid & 7;
-        const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+        const int gx = gridDim.x;
+        const int logical = dgq_xcd_logical(blockIdx.x + gx * blockIdx.y, gx * gridDim.y);
         bh = logical / gx;
         bx = logical - bh * gx;
     }

@@ -4,6 +4,8 @@
 #include <hip/hip_fp16.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
+#include <atomic>
+#include <initializer_list>
 #include "../../include/dgq_hip.h"
 
 void dgq_set_error(const char* fmt, ...);
@@ -23,6 +25,31 @@ static inline int dgq_launch_status(const char* what) {
         return DGQ_ELAUNCH;
     }
     return DGQ_OK;
+}
+
+// "Allow this much dynamic LDS for these kernels, once per device": `done` is the caller's static flag array (one per kernel
+// instantiation, or per group of kernels that launch together), indexed by device ordinal.  The attribute is per device and the
+// call idempotent, so a benign race at worst repeats it.
+struct DgqLdsAttr {
+    const void* kernel;
+    int bytes;
+    template <typename K> DgqLdsAttr(K* k, int b) : kernel(reinterpret_cast<const void*>(k)), bytes(b) {}
+};
+static inline void dgq_allow_dynamic_lds(std::atomic<bool> (&done)[64], std::initializer_list<DgqLdsAttr> kernels) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
+        for (const DgqLdsAttr& k : kernels) (void)hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes);
+        if (dev >= 0 && dev < 64) done[dev].store(true, std::memory_order_release);
+    }
+}
+
+// XCD-contiguous logical index of workgroup `bid` of a launch of T.  Workgroups are dealt round-robin over the 8 XCDs (each with its
+// own L2); remapped so that XCD k owns a contiguous range of logical indices (bijective for any T): neighbours in the logical order
+// then share what they read in ONE L2.
+__device__ __forceinline__ int dgq_xcd_logical(int bid, int T) {
+    const int q = T >> 3, r = T & 7, xcd = bid & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
 
 typedef int v4i __attribute__((ext_vector_type(4)));

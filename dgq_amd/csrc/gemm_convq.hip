@@ -13,24 +13,19 @@
 //      and quantise the slab's codes from the patch through the kpat table straight into the slab's LDS image — the same lane
 //      mapping and arithmetic as quant_act_conv_kernel (dgq_affine_code4_fast, quant_common.h), so codes AND row sums are the
 //      two-launch form's bit for bit — and
-//   3. run the slab's K tiles of gemm_panel_kernel's loop: A fragments from LDS, int4 weights streamed fragment-major into registers
+//   3. run the slab's K tiles of the quantise-on-load K loop (gemm_wfrag.h): A fragments from LDS, int4 weights streamed fragment-major into registers
 //      (hand-counted waits; the stream runs on across the slab switches), per-K group flushes by summation by parts;
 //   4. the dequantising store epilogue of the family (gemm_tile.h, TILED row mapping: residual / temb rows / GroupNorm partials).
 // No code matrix, no row-sum vector, one launch instead of two.  LDS (C = 320, Kp = 3072): patch 75 KB + tables 8 KB + slab 40 KB +
 // epilogue vectors 6 KB.  Layers it takes (dgq_gemm_conv_act_fuses): 3x3, stride 1, pad 1, W4, N % 32 == 0 and N <= 320, H % 4 == 0,
 // W % 8 == 0, patch + tables + a 10-tile slab within 160 KB (C <= 340) — the C = 320 convolutions of the 64 x 64 level of SD.  Layers with
 // more input channels (the concatenated up-path inputs, the 32 x 32 level) keep the two-launch form: their patch alone exceeds the LDS.
-#include "gemm_tile.h"
+#include "gemm_wfrag.h"
 #include "quant_common.h"
 
 DGQ_DIAG_BUFFER(convq)
 
 namespace {
-
-template <int N>
-__device__ __forceinline__ void cq_wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 constexpr int CQ_TH = 4, CQ_TW = 8;                      // output positions per workgroup: one 32-row MFMA tile
 __host__ __device__ constexpr int cq_align16(int v) { return (v + 15) & ~15; }
@@ -57,7 +52,6 @@ template <bool PER_M, typename TIO, int NW>
 __global__ __launch_bounds__(64 * NW) void gemm_convq_kernel(GemmBatch bt, int slab_tiles) {
     constexpr int BM = 32, BN = 32 * NW, NT = 64 * NW;
     constexpr int ACCS = PER_M ? 1 : 2;
-    constexpr int DT = 4, NS = DT + 1;
     const GemmParams& p = bt.p[0];
     gemm_prefetch_params(p);
     DGQ_DIAG_DECL
@@ -67,12 +61,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_convq_kernel(GemmBatch bt, int s
     const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
     const int tiles_w = Wo / CQ_TW, tiles_h = Ho / CQ_TH;
     // XCD-aware tile order: XCD k owns a contiguous range of tiles (neighbours share their halo rows in one L2)
-    int tile;
-    {
-        const int T = gridDim.x, bid = blockIdx.x;
-        const int q = T >> 3, r = T & 7, xcd = bid & 7;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int tile = dgq_xcd_logical(blockIdx.x, gridDim.x);
     const int b = tile / (tiles_h * tiles_w);
     const int trem = tile - b * tiles_h * tiles_w;
     const int th = trem / tiles_w, tw = trem - th * tiles_w;
@@ -84,60 +73,24 @@ __global__ __launch_bounds__(64 * NW) void gemm_convq_kernel(GemmBatch bt, int s
     const int nk = p.Kp / BK;
     const ConvqLds L = convq_lds(C, kh, kw, stride, p.Kp, NW, slab_tiles, PER_M);
 
-    // ---- W stream (gemm_panel_kernel's): this wave's 32 columns, fragment-major, DT K tiles ahead in NS register slots
+    // ---- W stream (gemm_wfrag.h): this wave's 32 columns, fragment-major
     const int ntile32 = (p.N + 31) >> 5;
     const int jt = min(wid, ntile32 - 1);                  // a wave past N recomputes the last column tile and stores nothing
     const uint4* wsrc = reinterpret_cast<const uint4*>(p.wfrag) + ((int64_t)jt * (nk * 2)) * 64 + lane;
-    v4i wr[NS][2];
-    auto wload = [&](int t, v4i (&dst)[2]) {
-        const uint4* q = wsrc + (t * 2) * 64;
-        asm volatile("global_load_dwordx4 %0, %2, off\n\tglobal_load_dwordx4 %1, %2, off offset:1024"
-                     : "=&v"(dst[0]), "=&v"(dst[1]) : "v"(q) : "memory");
-    };
-#pragma unroll
-    for (int d = 0; d < DT; ++d)
-        if (d < nk) wload(d, wr[d]);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) wr[DT][j] = (v4i){0, 0, 0, 0};
+    v4i wr[WF_NS][2];
+    wfrag_start(wsrc, nk, wr);
 
-    // ---- epilogue vectors and flush coefficients (gemm_panel_kernel's tables, KW = 1)
+    // ---- epilogue vectors and flush coefficients (table: linear over the chunks; two sequences, one K range)
     float* vtab = reinterpret_cast<float*>(smem + L.vtab);   // [3][32]: R0 R1 R2 | [4][BN]: alpha zw gamma vn
     float* vcol = vtab + 3 * BM;
     float* ctab = vcol + 4 * BN;                              // per-K: [nk·4] flush coefficients | [nk] clear flags
-    constexpr int MYCH = NCH;
-    const int n_coef = PER_M ? 0 : nk * MYCH, n_tab = PER_M ? 0 : n_coef + nk;
-    struct CoefIdx { int g, gn, tl; bool is_coef, seq_last, tile_end, not_last_tile; };
-    auto coef_idx = [&](int e) {
-        CoefIdx x;
-        x.is_coef = e < n_coef;
-        const int ec = x.is_coef ? e : 0;
-        const int tc = ec / MYCH, ci = ec - tc * MYCH;
-        const int t = x.is_coef ? tc : e - n_coef;
-        x.g = tc * NCH + ci;
-        x.tile_end = (ci + ACCS >= MYCH);
-        x.seq_last = x.tile_end && tc == nk - 1;
-        x.gn = min(x.tile_end ? (tc + 1) * NCH + (ci + ACCS - MYCH) : x.g + ACCS, nk * NCH - 1);
-        x.tl = t * NCH + NCH - 1;
-        x.not_last_tile = t != nk - 1;
-        return x;
-    };
-    auto coef_val = [&](const CoefIdx& x, float d, float dn, uint32_t cf) {
-        const bool clr = (cf & 0xFF) == 2;
-        const float coef = (x.seq_last || (x.tile_end && clr)) ? d : d - dn;
-        const float flag = (x.not_last_tile && clr) ? 1.0f : 0.0f;
-        return x.is_coef ? coef : flag;
-    };
+    const int n_coef = PER_M ? 0 : nk * NCH, n_tab = PER_M ? 0 : n_coef + nk;
+    const FlushGeom fg = {ACCS, 0, nk, nk, 0};
+    auto tab_ref = [&](int e) { return flush_ref(fg, e < n_coef, e < n_coef ? e : 0, e - n_coef); };
     const bool has_col = tid < BN;
-    float c_vn = 0.0f, c_d = 0.0f, c_dn = 0.0f;
-    uint32_t c_cf = 0;
-    const int ncol = min(tid, p.N - 1);
-    float c_al = gload_f32(p.alpha + ncol), c_zw = gload_f32(p.zw + ncol), c_ga = gload_f32(p.gamma + ncol);
-    if constexpr (PER_M) c_vn = gload_f32(p.vn + ncol);
-    CoefIdx cx = {};
-    if constexpr (!PER_M) {
-        cx = coef_idx(min(tid, n_tab - 1));
-        c_d = gload_f32(p.cdelta + cx.g); c_dn = gload_f32(p.cdelta + cx.gn); c_cf = gload_u8(p.cflush + cx.tl);
-    }
+    GemmColRegs cr = gemm_cols_issue<PER_M>(p, min(tid, p.N - 1));
+    GemmFlushRegs fr = {};
+    if constexpr (!PER_M) fr = gemm_flush_issue(p, n_tab, tid, tab_ref);
 
     // ---- 1. the input patch (quant_act_conv_kernel's staging: wave w takes pixels w, w + NW, ...)
     // (every load below is an ordinary one: the asm loads above are all OLDER, so hipcc's counted waits for these stay correct)
@@ -207,18 +160,9 @@ __global__ __launch_bounds__(64 * NW) void gemm_convq_kernel(GemmBatch bt, int s
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the first W tiles and the tables
-    if (PER_M) asm volatile("" : "+v"(c_al), "+v"(c_zw), "+v"(c_ga), "+v"(c_vn));
-    else asm volatile("" : "+v"(c_al), "+v"(c_zw), "+v"(c_ga), "+v"(c_d), "+v"(c_dn), "+v"(c_cf));
-    __builtin_amdgcn_sched_barrier(0);
-    if (has_col) {
-        vcol[tid] = c_al; vcol[BN + tid] = c_zw; vcol[2 * BN + tid] = c_ga; vcol[3 * BN + tid] = c_vn;
-    }
+    gemm_cols_commit<PER_M, BN>(cr, vcol, tid, has_col);
     if constexpr (!PER_M) {
-        if (tid < n_tab) ctab[tid] = coef_val(cx, c_d, c_dn, c_cf);
-        for (int e = tid + NT; e < n_tab; e += NT) {
-            const CoefIdx x = coef_idx(e);
-            ctab[e] = coef_val(x, p.cdelta[x.g], p.cdelta[x.gn], p.cflush[x.tl]);
-        }
+        gemm_flush_commit<NT>(p, fr, ctab, n_tab, tid, tab_ref);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // (long K only: ordinary loads of the loop above)
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -233,62 +177,15 @@ __global__ __launch_bounds__(64 * NW) void gemm_convq_kernel(GemmBatch bt, int s
     for (int cg = 0; cg < NCH; ++cg) a_off[cg] = lr * BK + (((2 * cg + hh) ^ ((lr >> 1) & 7)) << 4);
     v16i acc[ACCS][1][1];
     v16f accf[1][1];
-    constexpr bool BIASED = !PER_M;
-    constexpr int ACC0 = BIASED ? DGQ_ACC_BIAS_I : 0;
+    constexpr int ACC0 = PER_M ? 0 : DGQ_ACC_BIAS_I;         // per-K (W4): totals carry DGQ_ACC_BIAS_I (gemm_device.h)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
 #pragma unroll
         for (int a = 0; a < ACCS; ++a) acc[a][0][0][r] = ACC0;
         accf[0][0][r] = 0.0f;
     }
-    auto flush = [&](const v16i (&ac)[1][1], float coef) {
-        const float sc = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, coef)));
-        if (sc != 0.0f) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) accf[0][0][r] = __builtin_fmaf(sc, dgq_total_to_float<BIASED>(ac[0][0][r]), accf[0][0][r]);
-        }
-    };
     float pend = 0.0f;
-    typedef float cvec_t __attribute__((ext_vector_type(NCH)));
-    const float* tclr = ctab + nk * MYCH;
-    auto tile_fn = [&](int t, int ts, const v4i& w0, const v4i& w1) {      // t: K tile, ts: its index inside the slab image
-        cvec_t cq;
-        float tc = 0.0f;
-        if (!PER_M) {
-            cq = *reinterpret_cast<const cvec_t*>(ctab + t * MYCH);
-            tc = tclr[t];
-        }
-        const uint8_t* sa = slab + ts * (BM * BK);
-#pragma unroll
-        for (int ci = 0; ci < NCH; ++ci) {
-            const v4i af = *reinterpret_cast<const v4i*>(sa + a_off[ci]);
-            const v4i& w = ci < 2 ? w0 : w1;
-            const uint32_t x = (uint32_t)((ci & 1) ? w[2] : w[0]), y = (uint32_t)((ci & 1) ? w[3] : w[1]);
-            const v4i bf = (v4i){(int)(x & 0x0F0F0F0Fu), (int)((x >> 4) & 0x0F0F0F0Fu), (int)(y & 0x0F0F0F0Fu), (int)((y >> 4) & 0x0F0F0F0Fu)};
-            if constexpr (PER_M) {
-                acc[0][0][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af, bf, acc[0][0][0], 0, 0, 0);
-            } else {
-                if (ci & 1) {
-                    acc[1][0][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af, bf, acc[1][0][0], 0, 0, 0);
-                    flush(acc[0], pend);
-                } else {
-                    acc[0][0][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af, bf, acc[0][0][0], 0, 0, 0);
-                    flush(acc[1], pend);
-                }
-                pend = cq[ci];
-            }
-        }
-        if constexpr (!PER_M) {
-            if (__builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, tc)) != 0) {     // rare: a segment of running totals ends
-                flush(acc[1], pend);
-                pend = 0.0f;
-#pragma unroll
-                for (int a = 0; a < ACCS; ++a)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[a][0][0][r] = ACC0;
-            }
-        }
-    };
+    const float* tclr = ctab + nk * NCH;
     // the rows this wave quantises: wid, wid + NW, ... < 32; their running row sums live across the slabs
     constexpr int RQ = (32 + NW - 1) / NW;
     float partial[RQ];
@@ -325,8 +222,8 @@ __global__ __launch_bounds__(64 * NW) void gemm_convq_kernel(GemmBatch bt, int s
             partial[q] = part;
         }
     };
-    for (int tb = 0; tb < nk; tb += NS) {
-        if (tb % slab_tiles == 0) {                          // (slab_tiles is a multiple of NS: a slab starts at sl == 0 only)
+    for (int tb = 0; tb < nk; tb += WF_NS) {
+        if (tb % slab_tiles == 0) {                          // (slab_tiles is a multiple of WF_NS: a slab starts at sl == 0 only)
             DGQ_STAMP_NOW(dg_s0);
             if (tb > 0) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's reads of the previous slab are complete ...
@@ -343,23 +240,15 @@ __global__ __launch_bounds__(64 * NW) void gemm_convq_kernel(GemmBatch bt, int s
         }
         const int ts0 = tb % slab_tiles;
 #pragma unroll
-        for (int sl = 0; sl < NS; ++sl) {
-            const int t = tb + sl;
+        for (int sl = 0; sl < WF_NS; ++sl) {
+            const int t = tb + sl;                            // K tile t: tile ts0 + sl of the slab image
             if (t < nk) {                                     // wave-uniform
-                if (t + DT < nk) wload(t + DT, wr[(sl + DT) % NS]);
-                const int young = min(DT, nk - 1 - t);
-                if (young >= 4) cq_wait_vmcnt<8>();
-                else if (young == 3) cq_wait_vmcnt<6>();
-                else if (young == 2) cq_wait_vmcnt<4>();
-                else if (young == 1) cq_wait_vmcnt<2>();
-                else cq_wait_vmcnt<0>();
-                asm volatile("" : "+v"(wr[sl][0]), "+v"(wr[sl][1]));       // the slot's registers are defined HERE for the compiler
-                __builtin_amdgcn_sched_barrier(0);
-                tile_fn(t, ts0 + sl, wr[sl][0], wr[sl][1]);
+                wfrag_acquire(wsrc, t, nk, wr, sl);
+                wfrag_tile<PER_M>(slab + (ts0 + sl) * (BM * BK), a_off, ctab + t * NCH, tclr + t, wr[sl][0], wr[sl][1], acc, accf, pend);
             }
         }
     }
-    if constexpr (!PER_M) flush(acc[1], pend);
+    if constexpr (!PER_M) gemm_flush<true>(accf, acc[1], pend);
     DGQ_STAMP(6);
     // the rows' epilogue constants R0 R1 R2 (row sums complete: every slab has been quantised)
 #pragma unroll
@@ -389,12 +278,7 @@ int launch_convq(const GemmBatch& bt, int slab_tiles, int lds, hipStream_t st) {
     const dgq_gemm_act_t& a = bt.p[0].act;
     const int Ho = (a.H + 2 * a.pad - a.kh) / a.stride + 1, Wo = (a.W + 2 * a.pad - a.kw) / a.stride + 1;
     static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_convq_kernel<PER_M, TIO, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
-    }
+    dgq_allow_dynamic_lds(attr_set, {{&gemm_convq_kernel<PER_M, TIO, NW>, 160 * 1024}});
     const dim3 grid(a.B * (Ho / CQ_TH) * (Wo / CQ_TW)), block(64 * NW);
     hipLaunchKernelGGL((gemm_convq_kernel<PER_M, TIO, NW>), grid, block, lds, st, bt, slab_tiles);
     return DGQ_OK;

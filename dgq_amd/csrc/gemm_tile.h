@@ -1,6 +1,8 @@
 // Shared by the W4A8 / W8A8 GEMM kernels of libdgq_hip.so (gemm_wxa8.hip: the tile family of the layer shapes of a UNet step;
-// gemm_wxa8_big.hip: the 256-row ping-pong kernel for the compute-bound shapes): launch parameters, prologue helpers and the
-// dequantising store epilogue — ONE implementation, so that every kernel's results agree bit for bit.
+// gemm_wxa8_big.hip: the 256-row ping-pong kernel for the compute-bound shapes; gemm_panel.hip / gemm_convq.hip: the quantise-on-load
+// kernels): launch parameters, the prologue's table staging (epilogue column vectors; flush coefficients by the formula of
+// gemm_flush.h), the per-K flush / clear of the running totals and the dequantising store epilogue — ONE implementation, so that
+// every kernel's results agree bit for bit.  (gemm_wfrag.h: the W4 register stream and K tile of the two quantise-on-load kernels.)
 #pragma once
 #include <atomic>
 #include <cstdio>
@@ -8,10 +10,10 @@
 #include <type_traits>
 #include "dgq_common.h"
 #include "gemm_device.h"
+#include "gemm_flush.h"       // NCH (32-wide chunks per K tile) and the flush-coefficient formula
 #include "diag.h"
 
 #define BK 128
-#define NCH 4                 // 32-wide chunks per K tile
 
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef float v16f __attribute__((ext_vector_type(16)));
@@ -115,6 +117,72 @@ __device__ __forceinline__ void wait_ring(int tiles) {
     else if (MAXT >= 2 && tiles == 2) wait_vmcnt_lgkm0<PER * (MAXT >= 2 ? 2 : 0)>();
     else if (MAXT >= 3 && tiles == 3) wait_vmcnt_lgkm0<PER * (MAXT >= 3 ? 3 : 0)>();
     else wait_vmcnt_lgkm0<PER * (MAXT >= 4 ? 4 : 0)>();
+}
+
+// ---- prologue tables, staged in two halves: *_issue sends the asm loads (all unconditional, at clamped indices: a load whose address
+// or predicate depended on another load's result cost a full round trip each) and returns their registers; the KERNEL then places its
+// own wait (the tile kernel's counted wait_ring, vmcnt(0) elsewhere); *_commit defines the registers for the compiler (volatile asm
+// statements keep their order: behind that wait) and stores to LDS.
+struct GemmColRegs { float al, zw, ga, vn; };               // alpha zw gamma vn of one output column
+template <bool PER_M>
+__device__ __forceinline__ GemmColRegs gemm_cols_issue(const GemmParams& p, int n) {
+    GemmColRegs c;
+    c.al = gload_f32(p.alpha + n); c.zw = gload_f32(p.zw + n); c.ga = gload_f32(p.gamma + n);
+    c.vn = 0.0f;
+    if constexpr (PER_M) c.vn = gload_f32(p.vn + n);
+    return c;
+}
+template <bool PER_M, int BN>
+__device__ __forceinline__ void gemm_cols_commit(GemmColRegs& c, float* vcol, int tid, bool has_col) {
+    if (PER_M) asm volatile("" : "+v"(c.al), "+v"(c.zw), "+v"(c.ga), "+v"(c.vn));
+    else asm volatile("" : "+v"(c.al), "+v"(c.zw), "+v"(c.ga));
+    __builtin_amdgcn_sched_barrier(0);
+    if (has_col) {
+        vcol[tid] = c.al; vcol[BN + tid] = c.zw; vcol[2 * BN + tid] = c.ga; vcol[3 * BN + tid] = c.vn;
+    }
+}
+// Flush table (per-K): n_tab entries, thread tid takes entry tid by asm loads and entries tid + NT, tid + 2·NT, ... (long K only) by
+// ordinary ones.  `ref` is the kernel's map from table position to FlushRef (gemm_flush.h).
+struct GemmFlushRegs { FlushRef x; float d, dn; uint32_t cf; };
+template <typename Ref>
+__device__ __forceinline__ GemmFlushRegs gemm_flush_issue(const GemmParams& p, int n_tab, int tid, Ref&& ref) {
+    GemmFlushRegs f;
+    f.x = ref(min(tid, n_tab - 1));
+    f.d = gload_f32(p.cdelta + f.x.g); f.dn = gload_f32(p.cdelta + f.x.gn); f.cf = gload_u8(p.cflush + f.x.tl);
+    return f;
+}
+template <int NT, typename Ref>
+__device__ __forceinline__ void gemm_flush_commit(const GemmParams& p, GemmFlushRegs& f, float* ctab, int n_tab, int tid, Ref&& ref) {
+    asm volatile("" : "+v"(f.d), "+v"(f.dn), "+v"(f.cf));
+    __builtin_amdgcn_sched_barrier(0);
+    if (tid < n_tab) ctab[tid] = flush_value(f.x, f.d, f.dn, f.cf);
+    for (int e = tid + NT; e < n_tab; e += NT) ctab[e] = flush_entry(ref(e), p.cdelta, p.cflush);
+}
+
+// accf += coef · float(running total); coef is wave-uniform and 0 inside a group (nothing to add)
+template <bool BIASED, int TM, int TN>
+__device__ __forceinline__ void gemm_flush(v16f (&accf)[TM][TN], const v16i (&ac)[TM][TN], float coef) {
+    const float sc = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, coef)));
+    if (sc != 0.0f) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) accf[i][j][r] = __builtin_fmaf(sc, dgq_total_to_float<BIASED>(ac[i][j][r]), accf[i][j][r]);
+    }
+}
+// behind a K tile that carries a clear flag: every accumulator set starts again at ACC0
+template <int ACC0, int ACCS, int TM, int TN>
+__device__ __forceinline__ void gemm_clear_totals(v16i (&acc)[ACCS][TM][TN]) {
+#pragma unroll
+    for (int a = 0; a < ACCS; ++a)
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[a][i][j][r] = ACC0;
 }
 
 

@@ -55,10 +55,8 @@ void gemm_wxa8_kernel(GemmBatch bt) {
     // from its L2 by the other n tiles; only the (small) weight matrix is read by all eight.  Bijective for any grid size.
     int tile_n, tile_m;
     {
-        const int gx = gridDim.x, T = gridDim.x * gridDim.y;
-        const int bid = blockIdx.x + gx * blockIdx.y;
-        const int q = T >> 3, r = T & 7, xcd = bid & 7;
-        const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+        const int gx = gridDim.x;
+        const int logical = dgq_xcd_logical(blockIdx.x + gx * blockIdx.y, gx * gridDim.y);
         tile_m = logical / gx;
         tile_n = logical - tile_m * gx;
     }
@@ -229,52 +227,28 @@ void gemm_wxa8_kernel(GemmBatch bt) {
     float* vcol = vtab + 3 * BM;
     float* ctab = vcol + 4 * BN;                                           // [WVK][nk·MYCH] flush coefficients | [nk] clear flags
     static_assert(BM <= NT && BN <= NT, "one row / column of the epilogue vectors per thread");
-    // Summation by parts: with T the RUNNING int32 total of a chunk sequence and δ_c the scale of chunk c's group,
-    // Σ_groups δ_g·P_g = Σ_c (δ_c − δ_next(c))·T_c, δ := 0 past the sequence.  The coefficient is non-zero exactly at group
-    // ends, so a flush is cvt + fma per accumulator register.  A wave runs ACCS sequences (chunk ci of a tile belongs to
-    // sequence ci mod ACCS), the workgroup WVK·ACCS.  A clear mark (cflush == 2) on the LAST chunk of a K tile asks for the
-    // totals to be cleared behind that tile (|T| < 2^24: float(T) exact, dgq_amd/plan.py:mark_clears): the coefficient of each
-    // sequence's last chunk in the tile is then the full δ_c.  Marks on other chunks are not honoured (the planner places none).
-    // Table entries e < n_coef: coefficient of chunk i of wave kq;  e >= n_coef: clear flag of tile e − n_coef.
+    // Flush coefficients (summation by parts, gemm_flush.h): a wave runs ACCS sequences (chunk ci of a tile belongs to sequence
+    // ci mod ACCS), the workgroup WVK·ACCS.  Table entries e < n_coef: coefficient of chunk i of K wave kq (regrouped per K wave, so
+    // that a wave reads its MYCH coefficients of a tile as one vector); e >= n_coef: clear flag of tile e − n_coef.
     const int per_wave = nk * MYCH, n_coef = PER_M ? 0 : WVK * per_wave, n_tab = PER_M ? 0 : n_coef + nk;
-    struct CoefIdx { int g, gn, tl; bool is_coef, seq_last, tile_end, not_last_tile; };
-    auto coef_idx = [&](int e) {
-        CoefIdx x;
-        x.is_coef = e < n_coef;
-        const int ec = x.is_coef ? e : 0;
+    const FlushGeom fg = {ACCS * WVK, kt_begin, nk, nk_total, 0};
+    auto tab_ref = [&](int e) {
+        const int ec = e < n_coef ? e : 0;
         const int kq = ec / per_wave, i = ec - kq * per_wave;
         const int tc = i / MYCH, ci = i - tc * MYCH;
-        const int t = x.is_coef ? tc : e - n_coef;
-        x.g = (kt_begin + tc) * NCH + ci * WVK + kq;
-        x.tile_end = (ci + ACCS >= MYCH);                                    // last chunk of its sequence in the tile
-        x.seq_last = x.tile_end && tc == nk - 1;
-        x.gn = min(x.tile_end ? (kt_begin + tc + 1) * NCH + (ci + ACCS - MYCH) * WVK + kq : x.g + ACCS * WVK, nk_total * NCH - 1);
-        x.tl = (kt_begin + t) * NCH + NCH - 1;
-        x.not_last_tile = t + 1 < nk;
-        return x;
-    };
-    auto coef_val = [&](const CoefIdx& x, float d, float dn, uint32_t cf) {
-        const bool clr = (cf & 0xFF) == 2;
-        const float coef = (x.seq_last || (x.tile_end && clr)) ? d : d - dn;
-        const float flag = (x.not_last_tile && clr) ? 1.0f : 0.0f;
-        return x.is_coef ? coef : flag;
+        return flush_ref(fg, e < n_coef, (kt_begin + tc) * NCH + ci * WVK + kq, e - n_coef);
     };
     {
         const bool final_ep = (p.splits == 1);
         const bool has_row = final_ep && tid < BM, has_col = final_ep && tid < BN;
         const int m = min(m0 + tid, p.M - 1), n = min(n0 + tid, p.N - 1);
         const int li = PER_M ? m % p.L : 0;
-        float md = 1.0f, mz = 0.0f, c_vn = 0.0f, c_d = 0.0f, c_dn = 0.0f;
-        uint32_t c_cf = 0;
+        float md = 1.0f, mz = 0.0f;
         float rs = gload_f32(p.rowsum + m);
         if constexpr (PER_M) { md = gload_f32(p.mdelta + li); mz = gload_f32(p.mzp + li); }
-        float c_al = gload_f32(p.alpha + n), c_zw = gload_f32(p.zw + n), c_ga = gload_f32(p.gamma + n);
-        if constexpr (PER_M) c_vn = gload_f32(p.vn + n);
-        CoefIdx cx = {};
-        if constexpr (!PER_M) {
-            cx = coef_idx(min(tid, n_tab - 1));
-            c_d = gload_f32(p.cdelta + cx.g); c_dn = gload_f32(p.cdelta + cx.gn); c_cf = gload_u8(p.cflush + cx.tl);
-        }
+        GemmColRegs cr = gemm_cols_issue<PER_M>(p, n);
+        GemmFlushRegs fr = {};
+        if constexpr (!PER_M) fr = gemm_flush_issue(p, n_tab, tid, tab_ref);
         int issued = 0;
 #pragma unroll
         for (int i = 0; i < STAGES - 1; ++i)
@@ -284,8 +258,8 @@ void gemm_wxa8_kernel(GemmBatch bt) {
         wait_ring<DMA_PER_TILE, STAGES - 2>(issued - 1);
         DGQ_STAMP(4);
         // the loaded registers become defined HERE for the compiler (volatile asm statements keep their order)
-        if (PER_M) asm volatile("" : "+v"(rs), "+v"(md), "+v"(mz), "+v"(c_al), "+v"(c_zw), "+v"(c_ga), "+v"(c_vn));
-        else asm volatile("" : "+v"(rs), "+v"(c_al), "+v"(c_zw), "+v"(c_ga), "+v"(c_d), "+v"(c_dn), "+v"(c_cf));
+        if (PER_M) asm volatile("" : "+v"(rs), "+v"(md), "+v"(mz));
+        else asm volatile("" : "+v"(rs));
         __builtin_amdgcn_sched_barrier(0);
         if (has_row) {
             for (int j = 1; j < p.rowsum_parts; ++j) rs += p.rowsum[(int64_t)j * p.M + m];     // K-split quantise passes only
@@ -293,16 +267,8 @@ void gemm_wxa8_kernel(GemmBatch bt) {
             if (PER_M) { r0 = md; r1 = md * rs; r2 = md * (p.offset - mz); }
             vtab[tid] = r0; vtab[BM + tid] = r1; vtab[2 * BM + tid] = r2;
         }
-        if (has_col) {
-            vcol[tid] = c_al; vcol[BN + tid] = c_zw; vcol[2 * BN + tid] = c_ga; vcol[3 * BN + tid] = c_vn;
-        }
-        if constexpr (!PER_M) {
-            if (tid < n_tab) ctab[tid] = coef_val(cx, c_d, c_dn, c_cf);
-            for (int e = tid + NT; e < n_tab; e += NT) {    // long K only (ordinary loads: they drain the ring once)
-                const CoefIdx x = coef_idx(e);
-                ctab[e] = coef_val(x, p.cdelta[x.g], p.cdelta[x.gn], p.cflush[x.tl]);
-            }
-        }
+        gemm_cols_commit<PER_M, BN>(cr, vcol, tid, has_col);
+        if constexpr (!PER_M) gemm_flush_commit<NT>(p, fr, ctab, n_tab, tid, tab_ref);       // (long K: ordinary loads, they drain the ring once)
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the staging stores
     __builtin_amdgcn_s_barrier();
@@ -339,19 +305,7 @@ void gemm_wxa8_kernel(GemmBatch bt) {
             for (int j = 0; j < TN; ++j)
                 ac[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[i], bf[j], ac[i][j], 0, 0, 0);
     };
-    // accf += coef · float(running total); coef is wave-uniform and 0 inside a group (nothing to add)
-    auto flush = [&](const v16i (&ac)[TM][TN], float coef) {
-        const float sc = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, coef)));
-        if (sc != 0.0f) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) accf[i][j][r] = __builtin_fmaf(sc, dgq_total_to_float<BIASED>(ac[i][j][r]), accf[i][j][r]);
-                }
-        }
-    };
+    auto flush = [&](const v16i (&ac)[TM][TN], float coef) { gemm_flush<BIASED>(accf, ac, coef); };
     // one chunk step: MFMAs of chunk ci into its accumulator set, then the flush that is due — the chunk's own (ACCS = 1) or,
     // with two sets, the PREVIOUS chunk's (other set), whose MFMAs have had a whole step to finish
     float pend = 0.0f;                                      // ACCS = 2: coefficient of the chunk whose flush is pending
@@ -412,14 +366,7 @@ void gemm_wxa8_kernel(GemmBatch bt) {
         if (!PER_M) {
             if (__builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, tc)) != 0) {     // rare: a segment of running totals ends
                 if constexpr (ACCS == 2) { flush(acc[1], pend); pend = 0.0f; }
-#pragma unroll
-                for (int a = 0; a < ACCS; ++a)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) acc[a][i][j][r] = ACC0;
+                gemm_clear_totals<ACC0>(acc);
             }
         }
     }
@@ -589,21 +536,24 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(GemmParams p) {
     }
 }
 
-// gemm_wxa8_big.hip: the 256-row ping-pong kernel (W4, one problem, no K split); the plan names it by bm == 256
+// gemm_wxa8_big.hip: the 256-row ping-pong kernel (W4, one problem, no K split)
 int dgq_launch_gemm_big(const GemmBatch& bt, bool per_m, int y_dtype, hipStream_t st);
 size_t dgq_gemm_big_lds_bytes(bool per_m, int Kp);
 // gemm_panel.hip: the quantise-on-load kernel (the workgroup's 32 rows x the whole K quantised into an LDS panel, weights streamed
-// fragment-major into registers); the plan names it by bm = PANEL_BM0 + TM (wave tile rows / 32), bn = column waves per workgroup
-#define PANEL_BM0 1000
-int dgq_launch_gemm_panel(const GemmBatch& bt, bool per_m, int y_dtype, int tm, int nw, int kw, hipStream_t st);
-size_t dgq_gemm_panel_lds_bytes(int tm, int nw, int kw, bool per_m, int tiles);
+// fragment-major into registers): NW column waves x KW K waves per workgroup
+int dgq_launch_gemm_panel(const GemmBatch& bt, bool per_m, int y_dtype, int nw, int kw, hipStream_t st);
+size_t dgq_gemm_panel_lds_bytes(int nw, int kw, bool per_m, int tiles);
 // gemm_convq.hip: a 3x3 convolution with its activation quantiser inside the launch (act.kh > 1): slab length / LDS bytes, 0 = not taken
 int dgq_gemm_convq_plan(int B, int H, int W, int C, int kh, int kw, int stride, int pad, int N, int Kp, int w_bits, bool per_m, int* lds_bytes);
 int dgq_launch_gemm_convq(const GemmBatch& bt, bool per_m, int y_dtype, int slab_tiles, int lds, hipStream_t st);
 
 template <bool PER_M, typename TOut>
 static void launch_combine(const GemmParams& p, hipStream_t st);
-struct GemmPlan { int bm, bn, splits; double t; int kw = 1; bool fuse = false; };   // kw / fuse: the panel kernel's K waves / quantise-on-load
+// Which kernel a plan means, and its workgroup tile: bm x bn of the tile family (launch_one); 256-row: gemm_big_kernel's own shapes;
+// panel: bm = 32·TM rows (TM = 1 is all there is; DGQ_GEMM_FORCE may name another, which is refused), bn = 32·NW columns, kw K waves.
+enum class GemmKind { Tile, Rows256, Panel };
+struct GemmPlan { int bm, bn, splits; double t; int kw = 1; bool fuse = false; GemmKind kind = GemmKind::Tile; };   // fuse: quantise-on-load
+static GemmPlan plan_rows256() { GemmPlan pl = {256, 256, 1, 0.0}; pl.kind = GemmKind::Rows256; return pl; }
 
 template <int WBITS, bool PER_M, typename TOut, int BM, int BN, int WVM, int WVN, int WVK, int NST>
 static void launch_tile(const GemmBatch& bt, hipStream_t st) {
@@ -615,16 +565,8 @@ static void launch_tile(const GemmBatch& bt, hipStream_t st) {
     constexpr int lds_stages = NST * gemm_stage_bytes(WBITS, BM, BN);
     constexpr int lds_vec = (3 * BM + 4 * BN) * 4;
     constexpr int lds_max = lds_stages + lds_vec + 32768;       // + epilogue vectors + per-chunk coefficients (<= 4096 chunks)
-    // the attribute is per device: one flag per device ordinal (set again by whichever thread gets there first — the
-    // call is idempotent, so a benign race at worst repeats it)
     static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_wxa8_kernel<WBITS, PER_M, TOut, BM, BN, WVM, WVN, WVK, NST, ACCS>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-        if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
-    }
+    dgq_allow_dynamic_lds(attr_set, {{&gemm_wxa8_kernel<WBITS, PER_M, TOut, BM, BN, WVM, WVN, WVK, NST, ACCS>, lds_max}});
     int maxN = 0, maxM = 0, max_tps = 0;
     for (int i = 0; i < bt.n; ++i) {
         maxN = bt.p[i].N > maxN ? bt.p[i].N : maxN;
@@ -636,11 +578,7 @@ static void launch_tile(const GemmBatch& bt, hipStream_t st) {
     if (p.cv.codes_in) {                                 // implicit im2col A operand: four tile shapes carry it (conv_tile)
         if constexpr (WBITS == 4 && PER_M && ((BM == 32 && BN == 64) || (BM == 64 && BN == 64) || (BM == 64 && BN == 128) || (BM == 128 && BN == 128))) {
             static std::atomic<bool> cattr[64];
-            if (dev < 0 || dev >= 64 || !cattr[dev].load(std::memory_order_acquire)) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_wxa8_kernel<WBITS, PER_M, TOut, BM, BN, WVM, WVN, WVK, NST, ACCS, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-                if (dev >= 0 && dev < 64) cattr[dev].store(true, std::memory_order_release);
-            }
+            dgq_allow_dynamic_lds(cattr, {{&gemm_wxa8_kernel<WBITS, PER_M, TOut, BM, BN, WVM, WVN, WVK, NST, ACCS, true>, lds_max}});
             hipLaunchKernelGGL((gemm_wxa8_kernel<WBITS, PER_M, TOut, BM, BN, WVM, WVN, WVK, NST, ACCS, true>), grid, block, lds, st, bt);
         }
         return;                                          // (other shapes: refused by dgq_gemm_wxa8 before it gets here)
@@ -658,8 +596,7 @@ static void launch_ring(const GemmBatch& bt, hipStream_t st) {
 
 // Tile shapes the host may pick (BM x BN, waves m x n x k):
 //   W4: 32x64 (1x2x2), 32x128 (1x4x1), 64x64 (2x2x1), 64x128 (1x4x1: a widened int4 fragment feeds two row tiles),
-//       128x64 (2x2x1), 128x128 (2x2x1); bm = 256 names the 256-row ping-pong kernel of gemm_wxa8_big.hip (the 128x256 tile of
-//       round 3 — equal to 128x128 on every shape, never planned — is gone)
+//       128x64 (2x2x1), 128x128 (2x2x1) (the 128x256 tile of round 3 — equal to 128x128 on every shape, never planned — is gone)
 //   W8 (a secondary configuration): 32x64, 64x64, 128x128
 template <int WBITS, bool PER_M, typename TOut>
 static int launch_one(const GemmBatch& bt, int bm, int bn, hipStream_t st) {
@@ -699,24 +636,24 @@ template <int WBITS, bool PER_M>
 static int launch_gemm(const GemmBatch& p, const GemmPlan& pl, int y_dtype, hipStream_t st) {
     const int bm = pl.bm, bn = pl.bn;
     int rc;
-    if (bm == 256) {
+    if (pl.kind == GemmKind::Rows256) {
         DGQ_CHECK_ARG(WBITS == 4 && p.n == 1 && p.p[0].splits == 1 && dgq_gemm_big_lds_bytes(PER_M, p.p[0].Kp) <= 160 * 1024,
                       "dgq_gemm_wxa8: the 256-row kernel takes one unsplit W4 problem whose tables fit the LDS");
         rc = dgq_launch_gemm_big(p, PER_M, y_dtype, st);
         if (rc != DGQ_OK) return rc;
         return dgq_launch_status("dgq_gemm_wxa8");
     }
-    if (bm > PANEL_BM0) {
-        const int tm = bm - PANEL_BM0, nw = bn;
+    if (pl.kind == GemmKind::Panel) {
+        const int tm = bm / 32, nw = bn / 32;
         DGQ_CHECK_ARG(WBITS == 4 && pl.fuse, "dgq_gemm_wxa8: the panel kernel is the quantise-on-load form of W4 layers");
         for (int i = 0; i < p.n; ++i) {
             DGQ_CHECK_ARG(p.p[i].wfrag && !p.p[i].cv.codes_in && p.p[i].act.x, "dgq_gemm_wxa8: quantise-on-load needs the fragment-major weights (extra.wfrag) and the activation descriptor (extra.act)");
-            const size_t need = dgq_gemm_panel_lds_bytes(tm, nw, pl.kw, PER_M, p.p[i].tiles_per_split);
+            const size_t need = tm == 1 ? dgq_gemm_panel_lds_bytes(nw, pl.kw, PER_M, p.p[i].tiles_per_split) : 0;
             DGQ_CHECK_ARG(need > 0 && need <= 160 * 1024, "dgq_gemm_wxa8: no panel configuration TM=%d NW=%d KW=%d for a K extent of %d tiles",
                           tm, nw, pl.kw, p.p[i].tiles_per_split);
             DGQ_CHECK_ARG(p.p[i].splits == 1, "dgq_gemm_wxa8: quantise-on-load takes the whole K extent in one workgroup");
         }
-        rc = dgq_launch_gemm_panel(p, PER_M, y_dtype, tm, nw, pl.kw, st);
+        rc = dgq_launch_gemm_panel(p, PER_M, y_dtype, nw, pl.kw, st);
         if (rc != DGQ_OK) return rc;
         return dgq_launch_status("dgq_gemm_wxa8");
     }
@@ -763,7 +700,7 @@ static GemmPlan plan_gemm(int M, int N, int Kp, int w_bits, size_t ws_bytes, boo
     } else if (M >= 4096 && nk >= 24) {
         pl = (N % 128 != 0) ? GemmPlan{64, 64, 1, 0.0} : GemmPlan{32, 128, 1, 0.0};   // 8192x320x2880: 28 -> 25 us at 64x64
     }
-    // The 256-row ping-pong kernel (gemm_wxa8_big.hip; bm = 256 names it): W4, one unsplit problem.  One workgroup per CU and no
+    // The 256-row ping-pong kernel (gemm_wxa8_big.hip): W4, one unsplit problem.  One workgroup per CU and no
     // overlap between a workgroup's store epilogue and the next one's prologue, so it needs (a) at least one full round of
     // 256x256 (per-M) / 256x128 (per-K) tiles over the 256 CUs with N a whole number of tiles, and (b) enough work per tile:
     // K >= 4096, or — per-M — a wide N (>= 4096).  Measured in the model (SDXL C5, fp32 outputs with residual / GroupNorm
@@ -776,7 +713,7 @@ static GemmPlan plan_gemm(int M, int N, int Kp, int w_bits, size_t ws_bytes, boo
         constexpr long min_tiles = 256;
         if (allow_big && w_bits == 4 && pl.splits == 1 && M >= 2048 && N % bn_big == 0 && tiles >= min_tiles &&
             (nk >= 32 || (per_m && nk >= 8 && N >= 4096)) && dgq_gemm_big_lds_bytes(per_m, Kp) <= 160 * 1024)
-            pl = {256, 256, 1, 0.0};
+            pl = plan_rows256();
     }
     if (w_bits != 4) {                                   // W8 carries three tile shapes: nearest one
         if (pl.bm == 128 || pl.bn == 128) { pl.bm = 128; pl.bn = 128; }
@@ -798,14 +735,14 @@ static bool plan_panel_fuse(int M, int N, int Kp, bool per_m, GemmPlan& pl) {
     int nw;
     if (kw == 1) nw = (N % 320 == 0) ? 10 : 5;
     else nw = (N % 160 == 0) ? 5 : 4;
-    const size_t need = dgq_gemm_panel_lds_bytes(1, nw, kw, per_m, nk);
+    const size_t need = dgq_gemm_panel_lds_bytes(nw, kw, per_m, nk);
     if (need == 0 || need > 150 * 1024) return false;
     // every column block of a row block quantises the rows again: the fused form pays while that redundancy is small and the row
     // blocks alone fill the chip (tools/bench_fused.py, profiles/r05_fused_linear_shapes.txt); DGQ_GEMM_FUSE_ALL=1: wherever it fits
     const char* ea = getenv("DGQ_GEMM_FUSE_ALL");        // (read per call: the test suite switches it)
     const bool all = ea && *ea == '1';
     if (!all && ((N + 32 * nw - 1) / (32 * nw) > 2 || M < 2048)) return false;
-    pl.bm = PANEL_BM0 + 1; pl.bn = nw; pl.kw = kw; pl.fuse = true; pl.splits = 1;
+    pl.kind = GemmKind::Panel; pl.bm = 32; pl.bn = 32 * nw; pl.kw = kw; pl.fuse = true; pl.splits = 1;
     return true;
 }
 
@@ -828,6 +765,7 @@ extern "C" int dgq_gemm_conv_act_fuses(int B, int H, int W, int C, int kh, int k
 // per DMA piece, and the 64x64 tile the materialised operand prefers at M = 8192 has half the MFMAs per piece.
 static void conv_tile(GemmPlan& pl, int M) {
     const int key = pl.bm * 1000 + pl.bn;
+    pl.kind = GemmKind::Tile;
     if (M >= 2048) { pl.bm = 64; pl.bn = 128; return; }
     if (key == 32064 || key == 64064 || key == 64128 || key == 128128) return;
     if (pl.bm >= 128) { pl.bm = 128; pl.bn = 128; }
@@ -867,12 +805,14 @@ static bool forced_plan(GemmPlan& pl) {
     if (*e == 'F') {
         int kw = 1;
         if (sscanf(e + 1, "%d,%d,%d,%d", &bm, &bn, &s, &kw) < 3) return false;
-        bm += PANEL_BM0;
+        bm *= 32; bn *= 32;                              // TM, NW
+        pl.kind = GemmKind::Panel;
         pl.kw = kw < 1 ? 1 : kw;
         pl.fuse = true;
     } else if (sscanf(e, "%d,%d,%d", &bm, &bn, &s) != 3) {
         return false;
     } else {
+        pl.kind = bm == 256 ? GemmKind::Rows256 : GemmKind::Tile;     // "256,256,S": the 256-row kernel
         pl.fuse = false;
     }
     pl.bm = bm; pl.bn = bn; pl.splits = s < 1 ? 1 : s;

@@ -76,10 +76,8 @@ __global__ __launch_bounds__(BIG_NT, 2) void gemm_big_kernel(GemmBatch bt) {
     const uint64_t st_entry = BIG_STAMP == 2 ? big_stamp() : 0;      // BIG_STAMP = 2: block timeline (entry / loop start / loop end / stores issued / done)
     int tile_n, tile_m;
     {   // XCD-aware tile order (as gemm_wxa8_kernel): XCD k owns a contiguous m-major tile range
-        const int gx = gridDim.x, T = gridDim.x * gridDim.y;
-        const int bid = blockIdx.x + gx * blockIdx.y;
-        const int q = T >> 3, r = T & 7, xcd = bid & 7;
-        const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+        const int gx = gridDim.x;
+        const int logical = dgq_xcd_logical(blockIdx.x + gx * blockIdx.y, gx * gridDim.y);
         if (BIG_GROUP_M > 0) {
             constexpr int GM = BIG_GROUP_M > 0 ? BIG_GROUP_M : 1;
             const int gy = gridDim.y, band = logical / (GM * gx), first_m = band * GM;
@@ -192,22 +190,13 @@ __global__ __launch_bounds__(BIG_NT, 2) void gemm_big_kernel(GemmBatch bt) {
             vcol[3 * BN + tid] = PER_M ? p.vn[n] : 0.0f;
         }
         if constexpr (!PER_M) {
-            // Summation by parts (gemm_wxa8.hip): accf += (δ_c − δ_next)·float(running total) at every chunk; the coefficient is
-            // non-zero at group ends only.  A clear mark on a K tile's last chunk makes that chunk's coefficient the full δ_c and
-            // asks for the totals to be cleared behind the tile.
+            // the flush table of gemm_flush.h, one sequence (S = 1), linear over the chunks; read by the K loop where the caller did
+            // not bind its own (p.ccoef = plan.flush_coefficients, the same table)
             const int nchunk = nk * NCH;
-            for (int e = tid; e < nchunk + nk; e += NT) {
-                if (e < nchunk) {
-                    const int tcl = (e / NCH) * NCH + NCH - 1;                  // last chunk of this chunk's K tile
-                    const bool clr = (p.cflush[tcl] & 0xFF) == 2;
-                    const float d = p.cdelta[e], dn = p.cdelta[min(e + 1, nchunk - 1)];
-                    const bool full = (e == nchunk - 1) || (e == tcl && clr);
-                    ctab[e] = full ? d : d - dn;
-                } else {
-                    const int t = e - nchunk;
-                    ctab[e] = (t + 1 < nk && (p.cflush[t * NCH + NCH - 1] & 0xFF) == 2) ? 1.0f : 0.0f;
-                }
-            }
+            const FlushGeom fg = {1, 0, nk, nk, 0};
+#pragma unroll 1                                             // (rolled, as it always was: unrolled, it moves the K loop's register allocation)
+            for (int e = tid; e < nchunk + nk; e += NT)
+                ctab[e] = flush_entry(flush_ref(fg, e < nchunk, e < nchunk ? e : 0, e - nchunk), p.cdelta, p.cflush);
         }
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -413,13 +402,7 @@ void launch_big(const GemmBatch& bt, hipStream_t st) {
     const int nk = p.Kp / BK;
     const int lds = NBUF * stage + (3 * BM + 4 * BN) * 4 + (PER_M ? 0 : (((NCH + 1) * nk * 4 + 15) & ~15));
     static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_big_kernel<PER_M, TOut, BM, BN, NBUF>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
-    }
+    dgq_allow_dynamic_lds(attr_set, {{&gemm_big_kernel<PER_M, TOut, BM, BN, NBUF>, 160 * 1024}});
     dim3 grid((p.N + BN - 1) / BN, (p.M + BM - 1) / BM, 1), block(BIG_NT);
     hipLaunchKernelGGL((gemm_big_kernel<PER_M, TOut, BM, BN, NBUF>), grid, block, lds, st, bt);
 }

@@ -191,14 +191,9 @@ extern "C" int dgq_linear_smallm_batch(const void* x, int x_dtype, int M, int K,
     // codes [M][Kq] + row sums [16] + per wave a 32 x 65 int transposition scratch (66 KB at the M = 16, K = 2048 limits: opt in once)
     const size_t lds = ((((size_t)M * ((K + 15) & ~15)) + 15) & ~(size_t)15) + 64 + 4 * (32 * 65) * sizeof(int);
     static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_smallm_kernel<float, float>), hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_smallm_kernel<__half, __half>), hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_smallm_kernel<__hip_bfloat16, __hip_bfloat16>), hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
-        if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
-    }
+    dgq_allow_dynamic_lds(attr_set, {{&linear_smallm_kernel<float, float>, 72 * 1024},
+                                     {&linear_smallm_kernel<__half, __half>, 72 * 1024},
+                                     {&linear_smallm_kernel<__hip_bfloat16, __hip_bfloat16>, 72 * 1024}});
     hipStream_t st = (hipStream_t)stream;
 #define DGQ_SMALLM(TI, TO) hipLaunchKernelGGL((linear_smallm_kernel<TI, TO>), dim3(blocks), dim3(256), lds, st, b)
     if (x_dtype == DGQ_F32 && y_dtype == DGQ_F32) DGQ_SMALLM(float, float);

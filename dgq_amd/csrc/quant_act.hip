@@ -743,20 +743,13 @@ static void launch_quant_act(const QuantActBatch& bt, int n, int variant, bool p
         const int tiles = p0.B * ((p0.Ho + t.th - 1) / t.th) * ((p0.Wo + t.tw - 1) / t.tw);
         size_t lds5 = 0;
         for (int i = 0; i < n; ++i) lds5 = std::max(lds5, conv_lds_bytes(t, bt.p[i].Kp));
-        static std::atomic<bool> attr5[64];
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !attr5[dev].load(std::memory_order_acquire)) {          // all six instantiations of this dtype, once
-#define DGQ_QA_ATTR(PM, TH_, TW_) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_act_conv_kernel<TIn, PM, TH_, TW_, 8>), \
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, DGQ_QA_CONV_LDS_MAX)
-            DGQ_QA_ATTR(true, 4, 8); DGQ_QA_ATTR(false, 4, 8);
-#undef DGQ_QA_ATTR
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_act_conv_kernel<TIn, true, 4, 4, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, DGQ_QA_CONV_LDS_MAX);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_act_conv_kernel<TIn, false, 4, 4, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, DGQ_QA_CONV_LDS_MAX);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_act_conv_kernel<TIn, true, 2, 4, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, DGQ_QA_CONV_LDS_MAX);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_act_conv_kernel<TIn, false, 2, 4, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, DGQ_QA_CONV_LDS_MAX);
-            if (dev >= 0 && dev < 64) attr5[dev].store(true, std::memory_order_release);
-        }
+        static std::atomic<bool> attr5[64];                  // all six instantiations of this dtype, once
+        dgq_allow_dynamic_lds(attr5, {{&quant_act_conv_kernel<TIn, true, 4, 8, 8>, DGQ_QA_CONV_LDS_MAX},
+                                      {&quant_act_conv_kernel<TIn, false, 4, 8, 8>, DGQ_QA_CONV_LDS_MAX},
+                                      {&quant_act_conv_kernel<TIn, true, 4, 4, 16>, DGQ_QA_CONV_LDS_MAX},
+                                      {&quant_act_conv_kernel<TIn, false, 4, 4, 16>, DGQ_QA_CONV_LDS_MAX},
+                                      {&quant_act_conv_kernel<TIn, true, 2, 4, 16>, DGQ_QA_CONV_LDS_MAX},
+                                      {&quant_act_conv_kernel<TIn, false, 2, 4, 16>, DGQ_QA_CONV_LDS_MAX}});
 #define DGQ_QA_CONV(PM, TH_, TW_) hipLaunchKernelGGL((quant_act_conv_kernel<TIn, PM, TH_, TW_, 8>), dim3(tiles, 1, n), dim3(512), lds5, st, bt)
         if (t.id == 1) { if (per_m) DGQ_QA_CONV(true, 4, 8); else DGQ_QA_CONV(false, 4, 8); }
         else if (t.id == 2) {
@@ -782,14 +775,9 @@ static void launch_quant_act(const QuantActBatch& bt, int n, int variant, bool p
             lds = std::max(lds, tab + (variant == 3 ? 4 : 1) * (size_t)bt.p[i].Kp);
         }
         static std::atomic<bool> attr_set[64];
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_act_scatter_kernel<TIn, 4, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_act_scatter_kernel<TIn, 1, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&quant_act_scatter_kernel<TIn, 1, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-            if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
-        }
+        dgq_allow_dynamic_lds(attr_set, {{&quant_act_scatter_kernel<TIn, 4, 8>, 152 * 1024},
+                                         {&quant_act_scatter_kernel<TIn, 1, 8>, 152 * 1024},
+                                         {&quant_act_scatter_kernel<TIn, 1, 16>, 152 * 1024}});
         // four rows per block: two waves per row (the (tap, 256-channel) units dealt round-robin; each wave forms the row's LayerNorm
         // statistics itself) — a 2048-row launch is 2048 waves otherwise, two per SIMD, each a chain of dependent loads.
         // Rows (x problems) up to 2048 get 16 waves each instead of 8 (256 -> 2048 measured +0.5 % on the SD step, same box).

@@ -190,7 +190,8 @@ def plan_act(delta: torch.Tensor, zp: torch.Tensor, kind: str, C: int, taps: int
 
 def flush_coefficients(cdelta: torch.Tensor, cflush: torch.Tensor) -> torch.Tensor:
     """The per-chunk coefficients of the GEMM's summation by parts for an UNSPLIT launch, as the kernels form them in their
-    prologue (gemm_wxa8.hip / gemm_wxa8_big.hip): coef_c = δ_c − δ_{c+1} (non-zero at group ends only); the last chunk and the last
+    prologue (csrc/gemm_flush.h: this is its one-sequence case S = 1 over the whole K, and the Python statement
+    tests/test_flush_coef_cpu.py compares that header against): coef_c = δ_c − δ_{c+1} (non-zero at group ends only); the last chunk and the last
     chunk of a K tile that carries a clear mark (cflush == 2 on that tile's last chunk) take the full δ_c.  Followed by one clear
     flag per K tile (1.0 where the totals are cleared behind the tile; never behind the last).  fp32 [Kp/32 + Kp/128] — the
     256-row kernel reads it with scalar loads instead of testing a staged LDS table between its MFMAs."""
