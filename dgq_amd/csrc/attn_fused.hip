@@ -31,7 +31,8 @@ typedef float v16f __attribute__((ext_vector_type(16)));
 #define ATT_KT 32          // keys per tile
 #define LOG2E 1.4426950408889634f
 
-struct AttnParams {
+// (not AttnParams: that is the bf16x3 path's argument struct, an unrelated type in the same library)
+struct AttnF32Params {
     const float* q;
     const float* k;
     const float* v;
@@ -44,6 +45,8 @@ struct AttnParams {
     float* stats;          // [B*H][T][2] : m, l
     float* delta;          // device scalar
 };
+
+namespace {   // file-local: the bf16x3 path (attn_bf16x3_dev.h) has a key_of and a score_tile<D> of its own in the same library
 
 __device__ __forceinline__ int key_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
@@ -70,8 +73,10 @@ __device__ __forceinline__ v16f score_tile(const float* ks, const float (&qreg)[
     return acc;
 }
 
+}  // namespace
+
 template <int D>
-__global__ __launch_bounds__(256) void attn_stats_kernel(AttnParams p) {
+__global__ __launch_bounds__(256) void attn_stats_kernel(AttnF32Params p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* ks = lds;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, h32 = lane >> 5;
@@ -125,7 +130,7 @@ __global__ __launch_bounds__(256) void attn_stats_kernel(AttnParams p) {
 }
 
 template <int D>
-__global__ __launch_bounds__(256) void attn_pv_kernel(AttnParams p) {
+__global__ __launch_bounds__(256) void attn_pv_kernel(AttnF32Params p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int LD = D + 1;
     constexpr int NDT = (D + 31) / 32;                 // 32-wide d tiles of O^T
@@ -205,7 +210,7 @@ __global__ __launch_bounds__(256) void attn_pv_kernel(AttnParams p) {
 }
 
 template <int D>
-static int launch_attn(const AttnParams& p, hipStream_t st) {
+static int launch_attn(const AttnF32Params& p, hipStream_t st) {
     dim3 grid((p.T + ATT_QROWS - 1) / ATT_QROWS, p.B * p.H), block(256);
     const int lds1 = ATT_KT * (D + 1) * sizeof(float), lds2 = 2 * lds1;
     hipLaunchKernelGGL((attn_stats_kernel<D>), grid, block, lds1, st, p);
@@ -262,7 +267,7 @@ static int attention_impl(const void* q_, const void* k_, const void* v_, void* 
     DGQ_CHECK_ARG(mode >= 0 && mode <= 3 && skip >= 0 && skip < S && bits >= 2 && bits <= 8, "dgq_attention_f32: bad mode");
     DGQ_CHECK_ARG(mode < 2 || delta_in, "dgq_attention_f32: static modes need delta");
     hipStream_t st = (hipStream_t)stream;
-    AttnParams p;
+    AttnF32Params p;
     p.q = q; p.k = k; p.v = v; p.o = o; p.B = B; p.H = H; p.T = T; p.S = S; p.scale = scale; p.mode = mode; p.skip = skip;
     p.qmax = (float)((1 << bits) - 1); p.stats = stats_ws; p.delta = delta_ws;
     // quantised modes: bf16x3 MFMA path (fp32-equivalent accuracy, 16x the matrix rate); DGQ_ATTN_FP32=1 forces the
