@@ -46,6 +46,9 @@ SIGNATURES = {
     "dgq_act_row_params": [_vp, _i, _vp, ctypes.c_size_t, _vp, _vp, _vp],
     "dgq_act_row_params_batch": [_i, _vp, _vp, _vp],
     "dgq_quant_act_conv_tile": [_i, _i, _i, _i, _i, _vp],
+    "dgq_quant_act_block": [_vp, _vp, _vp],
+    "dgq_dequant_act_block": [_vp, _vp, _i, _i64, _i, _vp, _i, _vp],
+    "dgq_gemm_blockq": [_vp, _vp, _vp],
     "dgq_gemm_wxa8_batch": [_i, _vp, _vp],
     "dgq_adaround_soft_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
     "dgq_adaround_soft_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
@@ -95,6 +98,17 @@ class QuantActArgs(ctypes.Structure):
 class RowParamsOut(ctypes.Structure):
     """dgq_act_rowparams_out_t of include/dgq_hip.h"""
     _fields_ = [("fold_T", _i), ("ws", _vp), ("ws_floats", ctypes.c_size_t), ("delta", _vp), ("zp", _vp)]
+
+
+class ActBlockOut(ctypes.Structure):
+    """dgq_act_block_out_t of include/dgq_hip.h"""
+    _fields_ = [("codes", _vp), ("table", _vp), ("ldt", _i), ("rho", _vp)]
+
+
+class GemmBlock(ctypes.Structure):
+    """dgq_gemm_block_t of include/dgq_hip.h"""
+    _fields_ = [("table", _vp), ("ldt", _i), ("vc", _vp), ("B", _i), ("H", _i), ("W", _i), ("C", _i), ("kh", _i), ("kw", _i),
+                ("stride", _i), ("pad", _i), ("ups", _i)]
 
 
 class GemmArgs(ctypes.Structure):

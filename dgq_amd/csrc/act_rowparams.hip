@@ -38,15 +38,6 @@ struct RowParamsBatch {
     RowParamsProblem p[DGQ_RP_BATCH];
 };
 
-// MINMAX of one row from its extrema (0 already included): see the head of this file.  fp64 for the range and its division, one
-// rounding to fp32; IEEE fp32 division for z (no reciprocal).
-__device__ __forceinline__ void minmax_params(float lo, float hi, float levels, float& delta, float& zp) {
-    float d = (float)(((double)hi - (double)lo) / (double)levels);
-    if (d < 1e-8f) d = 1e-8f;
-    delta = d;
-    zp = rintf(__fdiv_rn(-lo, d));
-}
-
 template <typename TIn>
 __global__ __launch_bounds__(256) void rowparams_rows_kernel(RowParamsBatch bt) {
     const RowParamsProblem& p = bt.p[blockIdx.y];

@@ -1,0 +1,156 @@
+// Real-time activation quantiser per row and 32-channel block (a mode of this library; the reference has no such layer quantiser): every
+// block of DGQ_KCHUNK = 32 consecutive channels of every input row gets its own Scaler.MINMAX pair at run time — the statement is
+// dgq_amd/quant/quant_layer.py block_minmax (= row_minmax of the block's extrema) — so an outlier sets the step of its own 32 channels
+// only.  In the natural (tap, c) K order a 32-chunk of a convolution's unfolded row is 32 channels of ONE input pixel: the input is
+// quantised once per pixel and the unfolded operand never exists (dgq_gemm_blockq gathers the taps).
+//
+// One launch, one wave per input row (a Linear row or one pixel; rowparams_rows_kernel's mapping), nothing exchanged between waves:
+//   - the folded prologue (GroupNorm scale / shift, LayerNorm, SiLU, GEGLU) by the device functions of quant_prologue.h — the same x′
+//     bit for bit as the row mode and the calibrated quantisers see;
+//   - a lane holds 4 consecutive channels (one 16-byte load of fp32, clamped at the row end), 8 lanes one block: a 3-step in-wave
+//     min / max (0 included), then minmax_params;
+//   - codes by the exact-division arithmetic of quant_common.h: == clamp(rne(x/δ) + z, 0, 2^b − 1) under a true fp32 division;
+//   - written: centred int8 codes s = q − 2^(b−1) [rows][C] in natural order; {δ, β = δ·(2^(b−1) − z)} per block, [rows][ldt] float2
+//     (entries C/32 .. ldt − 1, the chunks of a Linear layer's K padding, are written {0, 0}); ρ[row] = Σ_c δ_c·rs_c with
+//     rs_c = Σ_{k∈c} s (an exact integer), added in ASCENDING block order c = 0, 1, ... by every lane alike (one fp32 addition per
+//     block, starting from 0): deterministic, and the order the CPU statement of the tests uses.
+// dgq_dequant_act_block: x̂ = δ·(q − z) from the codes and the table (the stand-alone fake-quant form of the quantizer).
+#include <cstdint>
+#include "dgq_common.h"
+#include "quant_prologue.h"
+
+struct BlockQuantProblem {
+    const void* x;
+    int rows, rows_per_image, C, ldc;
+    const float* pre_scale; const float* pre_shift; int pre_act;
+    const float* ln_gamma; const float* ln_beta; float ln_eps;
+    float levels, qmax, offset;
+    int8_t* codes; float2* table; int ldt; float* rho;
+};
+
+template <typename TIn>
+__global__ __launch_bounds__(256) void quant_block_kernel(BlockQuantProblem p) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= p.rows) return;                              // whole wave leaves; no barriers below
+    const TIn* xr = reinterpret_cast<const TIn*>(p.x) + (int64_t)row * p.ldc;
+    const int b = row / p.rows_per_image;
+    const float* pre_sc = p.pre_scale ? p.pre_scale + (int64_t)b * p.C : nullptr;
+    const float* pre_sh = p.pre_shift ? p.pre_shift + (int64_t)b * p.C : nullptr;
+    float ln_mu = 0.0f, ln_rstd = 1.0f;
+    if (p.ln_gamma) row_layernorm_stats<TIn>(xr, p.C, p.ln_eps, lane, ln_mu, ln_rstd);
+    int8_t* crow = p.codes + (int64_t)row * p.C;
+    float2* trow = p.table + (int64_t)row * p.ldt;
+    float rho = 0.0f;
+    // wave-uniform steps of 256 channels = 8 blocks; C % 32 == 0, so the 8 lanes of a block are all inside the row or all past it (a
+    // block past the end computes on a clamped address and stores nothing)
+    for (int base = 0; base < p.C; base += 256) {
+        const int c0 = base + lane * 4;
+        const bool in = c0 < p.C;
+        const int c = min(c0, p.C - 4);
+        float v[4], g[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        load4<TIn>(xr + c, v);
+        if (p.pre_act == 2) load4<TIn>(xr + p.C + c, g);
+        dgq_prologue4(v, c, pre_sc, pre_sh, p.ln_gamma, p.ln_beta, ln_mu, ln_rstd, p.pre_act, g);
+        float mn = fminf(0.0f, fminf(fminf(v[0], v[1]), fminf(v[2], v[3])));       // MINMAX includes 0 in the range
+        float mx = fmaxf(0.0f, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+#pragma unroll
+        for (int o = 1; o < 8; o <<= 1) {
+            mn = fminf(mn, __shfl_xor(mn, o, 64));
+            mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+        }
+        float d, z;
+        minmax_params(mn, mx, p.levels, d, z);
+        float q[4];
+        dgq_affine_code4_fast(v, d, dgq_rcp(d), z, p.qmax, q);
+        const float biased[4] = {q[0] - p.offset + 128.0f, q[1] - p.offset + 128.0f, q[2] - p.offset + 128.0f, q[3] - p.offset + 128.0f};
+        float fs = 0.0f;
+        const uint32_t w = dgq_pack4(biased, fs);
+        float rs = fs - 512.0f;                              // Σ s of the lane's four codes, then of the block (exact integers)
+#pragma unroll
+        for (int o = 1; o < 8; o <<= 1) rs += __shfl_xor(rs, o, 64);
+        if (in) {
+            *reinterpret_cast<uint32_t*>(crow + c) = w;
+            if ((lane & 7) == 0) trow[c >> 5] = make_float2(d, d * (p.offset - z));
+        }
+        const float term = d * rs;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {                        // ascending block order, the same chain in every lane
+            const float t = __shfl(term, 8 * j, 64);
+            if (base + 32 * j < p.C) rho += t;
+        }
+    }
+    for (int cb = (p.C >> 5) + lane; cb < p.ldt; cb += 64) trow[cb] = make_float2(0.0f, 0.0f);
+    if (lane == 0) p.rho[row] = rho;
+}
+
+extern "C" int dgq_quant_act_block(const dgq_quant_act_args_t* in, const dgq_act_block_out_t* out, void* stream) {
+    DGQ_CHECK_ARG(in && out, "dgq_quant_act_block: null pointer");
+    const dgq_quant_act_args_t& a = *in;
+    const dgq_act_block_out_t& o = *out;
+    DGQ_CHECK_ARG(a.x && o.codes && o.table && o.rho, "dgq_quant_act_block: null pointer");
+    DGQ_CHECK_ARG(((uintptr_t)a.x & 15) == 0 && ((uintptr_t)o.codes & 15) == 0 && ((uintptr_t)o.table & 7) == 0,
+                  "dgq_quant_act_block: x / codes must be 16-byte aligned, the table 8-byte aligned");
+    DGQ_CHECK_ARG(a.B > 0 && a.H > 0 && a.W > 0 && a.C > 0, "dgq_quant_act_block: bad geometry");
+    DGQ_CHECK_ARG(a.C % DGQ_KCHUNK == 0, "dgq_quant_act_block: C=%d must be a multiple of %d", a.C, DGQ_KCHUNK);
+    DGQ_CHECK_ARG(o.ldt >= a.C / DGQ_KCHUNK, "dgq_quant_act_block: table pitch %d < %d blocks", o.ldt, a.C / DGQ_KCHUNK);
+    DGQ_CHECK_ARG(a.bits >= 2 && a.bits <= 8, "dgq_quant_act_block: bits=%d", a.bits);
+    DGQ_CHECK_ARG((a.pre_scale == nullptr) == (a.pre_shift == nullptr) && a.pre_act >= 0 && a.pre_act <= 2, "dgq_quant_act_block: bad prologue");
+    const bool one = a.kh == 1 && a.kw == 1;
+    DGQ_CHECK_ARG(a.pre_act != 2 || (one && !a.pre_scale), "dgq_quant_act_block: GEGLU prologue is for Linear inputs");
+    DGQ_CHECK_ARG((a.ln_gamma == nullptr) == (a.ln_beta == nullptr), "dgq_quant_act_block: LayerNorm prologue needs gamma and beta");
+    DGQ_CHECK_ARG(!a.ln_gamma || (one && !a.pre_scale && a.pre_act == 0 && a.C <= DGQ_LN_MAX_C && a.ln_eps > 0.0f),
+                  "dgq_quant_act_block: LayerNorm prologue is for Linear inputs (1x1, C <= 2048, no other prologue)");
+    const int ups = a.ups ? 1 : 0;
+    DGQ_CHECK_ARG(!ups || (a.H % 2 == 0 && a.W % 2 == 0), "dgq_quant_act_block: ups needs even H, W");
+    const int Hs = a.H >> ups, Ws = a.W >> ups;
+    const int64_t rows = (int64_t)a.B * Hs * Ws;
+    DGQ_CHECK_ARG(rows < (1LL << 30) && rows * a.C < (1LL << 40), "dgq_quant_act_block: too many rows");
+    BlockQuantProblem p;
+    p.x = a.x; p.rows = (int)rows; p.rows_per_image = Hs * Ws; p.C = a.C; p.ldc = a.pre_act == 2 ? 2 * a.C : a.C;
+    p.pre_scale = a.pre_scale; p.pre_shift = a.pre_shift; p.pre_act = a.pre_act;
+    p.ln_gamma = a.ln_gamma; p.ln_beta = a.ln_beta; p.ln_eps = a.ln_eps;
+    p.levels = (float)((1 << a.bits) - 1); p.qmax = p.levels; p.offset = (float)(1 << (a.bits - 1));
+    p.codes = o.codes; p.table = reinterpret_cast<float2*>(o.table); p.ldt = o.ldt; p.rho = o.rho;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((p.rows + 3) / 4), block(256);
+    switch (a.x_dtype) {
+        case DGQ_F32: hipLaunchKernelGGL((quant_block_kernel<float>), grid, block, 0, st, p); break;
+        case DGQ_F16: hipLaunchKernelGGL((quant_block_kernel<__half>), grid, block, 0, st, p); break;
+        case DGQ_BF16: hipLaunchKernelGGL((quant_block_kernel<__hip_bfloat16>), grid, block, 0, st, p); break;
+        default: dgq_set_error("dgq_quant_act_block: unknown dtype %d", a.x_dtype); return DGQ_EINVAL;
+    }
+    return dgq_launch_status("dgq_quant_act_block");
+}
+
+// x̂ = δ·(q − z) of four codes per thread.  The table holds β = fl(δ·(o − z)) with o − z an integer of magnitude <= 2^b: rint(β / δ)
+// returns it exactly, and δ·(s + (o − z)) = δ·(q − z) is the reference's one rounding (quant_layer.py:299).
+template <typename TOut>
+__global__ __launch_bounds__(256) void dequant_block_kernel(const int8_t* codes, const float2* table, int ldt, int64_t rows, int C, TOut* y) {
+    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= rows * C) return;
+    const int64_t row = i / C;
+    const int c = (int)(i - row * C);
+    const float2 t = table[row * ldt + (c >> 5)];
+    const float oz = rintf(__fdiv_rn(t.y, t.x));
+    const uint32_t w = *reinterpret_cast<const uint32_t*>(codes + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) y[i + j] = dgq_from_float<TOut>(t.x * ((float)(int8_t)(w >> (8 * j)) + oz));
+}
+
+extern "C" int dgq_dequant_act_block(const int8_t* codes, const float* table, int ldt, int64_t rows, int C, void* y, int y_dtype, void* stream) {
+    DGQ_CHECK_ARG(codes && table && y, "dgq_dequant_act_block: null pointer");
+    DGQ_CHECK_ARG(rows > 0 && C > 0 && C % DGQ_KCHUNK == 0 && ldt >= C / DGQ_KCHUNK && rows * C < (1LL << 40),
+                  "dgq_dequant_act_block: bad shape rows=%lld C=%d ldt=%d", (long long)rows, C, ldt);
+    DGQ_CHECK_ARG(((uintptr_t)codes & 3) == 0 && ((uintptr_t)table & 7) == 0, "dgq_dequant_act_block: codes 4-byte, table 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((rows * C / 4 + 255) / 256)), block(256);
+    const float2* tb = reinterpret_cast<const float2*>(table);
+    switch (y_dtype) {
+        case DGQ_F32: hipLaunchKernelGGL((dequant_block_kernel<float>), grid, block, 0, st, codes, tb, ldt, rows, C, reinterpret_cast<float*>(y)); break;
+        case DGQ_F16: hipLaunchKernelGGL((dequant_block_kernel<__half>), grid, block, 0, st, codes, tb, ldt, rows, C, reinterpret_cast<__half*>(y)); break;
+        case DGQ_BF16: hipLaunchKernelGGL((dequant_block_kernel<__hip_bfloat16>), grid, block, 0, st, codes, tb, ldt, rows, C, reinterpret_cast<__hip_bfloat16*>(y)); break;
+        default: dgq_set_error("dgq_dequant_act_block: unknown dtype %d", y_dtype); return DGQ_EINVAL;
+    }
+    return dgq_launch_status("dgq_dequant_act_block");
+}

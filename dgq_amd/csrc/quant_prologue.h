@@ -64,3 +64,12 @@ __device__ __forceinline__ void dgq_prologue4(float (&v)[4], int c, const float*
         for (int j = 0; j < 4; ++j) v[j] = v[j] * (0.5f * g[j] * (1.0f + erff(g[j] * 0.70710678118654752f)));
     }
 }
+
+// MINMAX of one row from its extrema (0 already included): dgq_amd/quant/quant_layer.py row_minmax.  fp64 for the range and its division, one
+// rounding to fp32; IEEE fp32 division for z (no reciprocal).
+__device__ __forceinline__ void minmax_params(float lo, float hi, float levels, float& delta, float& zp) {
+    float d = (float)(((double)hi - (double)lo) / (double)levels);
+    if (d < 1e-8f) d = 1e-8f;
+    delta = d;
+    zp = rintf(__fdiv_rn(-lo, d));
+}

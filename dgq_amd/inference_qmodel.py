@@ -48,11 +48,18 @@ def parse_args(argv=None):
     p.add_argument("--aq_real_time", action="store_true",
                    help="with --use_aq: per-row activation parameters taken from every call's own rows (Scaler.MINMAX per row, "
                         "dgq_act_row_params) — runs from a weight-only checkpoint, no activation calibration")
+    p.add_argument("--aq_real_time_block", type=int, default=0,
+                   help="with --aq_real_time: 32 = one pair per row and block of 32 consecutive channels (dgq_quant_act_block + "
+                        "dgq_gemm_blockq); 0 = one pair per row")
     return p.parse_args(argv)
 
 
 def main(argv=None):
     opt = parse_args(argv)
+    if opt.aq_real_time_block and not (opt.use_aq and opt.aq_real_time):       # (a bad command line exits before anything is built)
+        raise SystemExit("--aq_real_time_block is a granularity of the real-time mode: it needs --use_aq --aq_real_time")
+    if opt.aq_real_time_block not in (0, 32):
+        raise SystemExit("--aq_real_time_block is 0 or 32")
     logging.basicConfig(level=logging.INFO)
     from .diffusers_rewrite import UNet2DConditionModel, ARCH
     from .quant import get_qmodel, Scaler
@@ -94,6 +101,8 @@ def main(argv=None):
     aq_params = {"bits": opt.aq, "channel_wise": False, "scaler": Scaler.MINMAX, "leaf_param": opt.use_aq}
     if real_time:
         aq_params["real_time"] = True
+        if opt.aq_real_time_block:
+            aq_params["real_time_block"] = opt.aq_real_time_block
     softmax_aq_params = {"softmax_a_bit": opt.aq, "t2i_log_quant": opt.t2i_log_quant,
                          "t2i_real_time": opt.t2i_real_time, "t2i_start_peak": opt.t2i_start_peak, "log_max_1": False}
     time_aware = opt.time_aware_aqtizer if opt.use_aq else False

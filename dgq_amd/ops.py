@@ -159,6 +159,7 @@ class PackedWeight:
         self._natural = None
         self._natural_frag = None
         self._vn = None
+        self._vc = None
 
     def natural_frag(self):
         """the natural-order weights fragment-major (dgq_pack_w4 layout 2), W4 only; None otherwise"""
@@ -182,12 +183,24 @@ class PackedWeight:
             self._vn = self.centered().sum(dim=1).float().contiguous()
         return self._vn
 
+    def vc(self):
+        """Vc[n][c] = Σ_{k∈c} (q − z) per 32-chunk c of the natural K order, fp32 [N][Kp/32] (integer-valued, 0 on the chunks of the
+        K padding) — the load-time table of dgq_gemm_blockq"""
+        if self._vc is None:
+            perm = natural_kperm(self.C, self.taps).to(self.codes.device).long()
+            cen = self.centered()
+            nat = torch.where(perm >= 0, cen[:, perm.clamp(min=0)], torch.zeros((), dtype=cen.dtype, device=cen.device))
+            self._vc = nat.view(self.N, -1, 32).sum(dim=2).float().contiguous()
+        return self._vc
+
 
 class ActBinding:
     """Device-resident tables of one (layer, timestep-slot) activation quantizer."""
 
     #: True on a DynamicActBinding whose row tables are not set yet (see there)
     dynamic = False
+    #: True on a BlockActBinding (see there): the layer runs dgq_quant_act_block + dgq_gemm_blockq
+    block = False
 
     def _table(self, key, make):
         if key not in self._koff:
@@ -313,6 +326,27 @@ class DynamicActBinding(ActBinding):
         ab.dynamic = False
         ab.mdelta, ab.mzp, ab.L = mdelta, mzp, mdelta.numel()
         return ab
+
+
+class BlockActBinding(ActBinding):
+    """The binding of a real-time BLOCK activation quantizer (UniformAffineQuantizer(real_time=True, real_time_block=32)): the
+    natural-order weight image and Vc (PackedWeight.vc), no tables, no timestep slots, one binding per layer.  quant_linear /
+    quant_conv2d / quant_linear_multi run such a layer as dgq_quant_act_block on its INPUT (once per row / pixel: codes, {δ, β} per
+    32-channel block, ρ) + dgq_gemm_blockq (a convolution gathers the taps; the unfolded operand never exists)."""
+
+    block = True
+
+    def __init__(self, pw: PackedWeight, abits: int):
+        assert pw.C % 32 == 0, "real-time block quantizer: C % 32 == 0"
+        self.mode, self.abits, self.offset = "block", abits, act_offset(abits)
+        self.pw = pw
+        self.wpacked, self.Kp = pw.natural()
+        self.wfrag = None
+        self.ksrc = None
+        self._koff = {}
+        self.L = 0
+        self.gamma = pw.bias
+        self.vc = pw.vc()
 
 
 # ------------------------------------------------------------------------------------------ hot path
@@ -823,6 +857,72 @@ def gemm_wxa8(codes, rowsum, M, ab: ActBinding, out_dtype, out: Optional[torch.T
     return out
 
 
+#: BLOCK_LAUNCH_HOOK(issue, kind, info): every launch of the real-time block mode — kind "quant" (dgq_quant_act_block; info = rows, C)
+#: or "gemm" (dgq_gemm_blockq; info = M, N, K).  A measurement hook (tools/profile_realtime_act.py), None in production.
+BLOCK_LAUNCH_HOOK = None
+
+
+def quant_act_block(x_cl: torch.Tensor, geom, bits, pre=None, ln=None, ups=False, ldt=None):
+    """dgq_quant_act_block on the layer INPUT x_cl (channels-last storage, geom = (B, H, W, C, kh, kw, stride, pad) as for quant_act):
+    one launch.  Returns (codes int8 [rows][C], table fp32 [rows][ldt][2] = {δ, β} per 32-channel block, ρ fp32 [rows]) with rows =
+    the input's rows / pixels (the SOURCE pixels with ``ups``); ldt (default C/32) > C/32 adds zeroed entries (a Linear layer's K
+    padding).  pre / ln / ups as in quant_act."""
+    B, H, W, C = geom[:4]
+    sh = 1 if ups else 0
+    rows = B * (H >> sh) * (W >> sh)
+    ldt = C // 32 if ldt is None else ldt
+    a, keep = _quant_input(x_cl, geom, bits, pre, ln, ups)
+    codes = torch.empty((rows, C), dtype=torch.int8, device=x_cl.device)
+    table = torch.empty((rows, ldt, 2), dtype=torch.float32, device=x_cl.device)
+    rho = torch.empty((rows,), dtype=torch.float32, device=x_cl.device)
+    o = _lib.ActBlockOut()
+    o.codes, o.table, o.ldt, o.rho = codes.data_ptr(), table.data_ptr(), ldt, rho.data_ptr()
+
+    def issue(_keep=(keep, codes, table, rho)):
+        _lib_call("dgq_quant_act_block", _c.byref(a), _c.byref(o), _lib.stream())
+    issue()
+    if BLOCK_LAUNCH_HOOK is not None:
+        BLOCK_LAUNCH_HOOK(issue, "quant", (rows, C))
+    return codes, table, rho
+
+
+def dequant_act_block(codes, table, out):
+    """out [rows][C] = δ·(q − z) from quant_act_block's codes and table (dgq_dequant_act_block)"""
+    rows, C = codes.shape
+    _lib_call("dgq_dequant_act_block", _lib.ptr(codes), _lib.ptr(table), table.shape[1], rows, C, _lib.ptr(out), _lib.DTYPE_CODE[out.dtype],
+              _lib.stream())
+    return out
+
+
+def gemm_blockq(q, geom, ab: "BlockActBinding", out_dtype, out=None, extra=None, ups=False):
+    """One dgq_gemm_blockq launch on q = quant_act_block(...) of the layer input; geom = (B, H, W, C, kh, kw, stride, pad) of the layer
+    (H, W: behind a folded upsample).  Returns y [M][N] (N/2 columns with the GEGLU epilogue)."""
+    codes, table, rho = q
+    B, H, W, C, kh, kw, stride, pad = geom
+    M = B * ((H + 2 * pad - kh) // stride + 1) * ((W + 2 * pad - kw) // stride + 1)
+    pw = ab.pw
+    if out is None:
+        out = torch.empty((M, pw.N // 2 if (extra is not None and extra.geglu) else pw.N), dtype=out_dtype, device=codes.device)
+    g = _lib.GemmArgs()
+    g.codes, g.rowsum, g.rowsum_parts = codes.data_ptr(), rho.data_ptr(), 1
+    g.M, g.Kp, g.wpacked, g.w_bits, g.N, g.per_m, g.L = M, ab.Kp, ab.wpacked.data_ptr(), pw.bits, pw.N, 0, 1
+    g.offset = ab.offset
+    g.alpha, g.zw, g.gamma = pw.alpha.data_ptr(), pw.zw.data_ptr(), ab.gamma.data_ptr()
+    g.y, g.y_dtype, g.ldy = out.data_ptr(), _lib.DTYPE_CODE[out.dtype], out.stride(0)
+    if extra is not None:
+        g.extra = _c.cast(_c.pointer(extra), _c.c_void_p)
+    k = _lib.GemmBlock()
+    k.table, k.ldt, k.vc = table.data_ptr(), table.shape[1], ab.vc.data_ptr()
+    k.B, k.H, k.W, k.C, k.kh, k.kw, k.stride, k.pad, k.ups = B, H, W, C, kh, kw, stride, pad, 1 if ups else 0
+
+    def issue(_keep=(q, out, extra, ab)):
+        _lib_call("dgq_gemm_blockq", _c.byref(g), _c.byref(k), _lib.stream())
+    issue()
+    if BLOCK_LAUNCH_HOOK is not None:
+        BLOCK_LAUNCH_HOOK(issue, "gemm", (M, pw.N, pw.K))
+    return out
+
+
 def quant_linear(x: torch.Tensor, ab: ActBinding, pre_act=0, residual=None, fq=None, ln=None, geglu=False):
     """x [..., K] -> [..., N].  pre_act: 0 none, 1 SiLU(x), 2 GEGLU (x is [..., 2K]: x[:K]·gelu(x[K:])) folded into the
     quantise-on-load pass; residual [..., N] and fq (see make_extra) folded into the GEMM epilogue.  geglu: the weight rows
@@ -839,6 +939,10 @@ def quant_linear(x: torch.Tensor, ab: ActBinding, pre_act=0, residual=None, fq=N
         res2 = residual.reshape(-1, ab.pw.N)
         if not res2.is_contiguous():
             res2 = res2.contiguous()
+    if ab.block:                                         # real-time block mode: quantise the rows once, one GEMM
+        geom = (rows, 1, 1, K, 1, 1, 1, 0)
+        y = gemm_blockq(quant_act_block(x2, geom, ab.abits, pre, ln, ldt=ab.Kp // 32), geom, ab, x.dtype, extra=make_extra(res2, fq, geglu=geglu))
+        return y.view(*x.shape[:-1], y.shape[-1])
     ab = _bind_rows(ab, x2, (rows, 1, 1, K, 1, 1, 1, 0), pre, ln)
     if pre_act != 2 and act_fuses(ab, rows, K, x.dtype, x2=x2):
         y = gemm_act(x2, rows, ab, x.dtype, extra=make_extra(res2, fq, geglu=geglu), pre=pre, ln=ln)
@@ -881,6 +985,21 @@ def quant_linear_multi(x: torch.Tensor, bindings, ln=None):
         x2 = x2.contiguous()
     M = x2.shape[0]
     dev = x2.device
+    if any(ab.block for ab in bindings):                # real-time block layers: the shared input is quantised ONCE per bit width, one GEMM each
+        geom = (M, 1, 1, Kin, 1, 1, 1, 0)
+        quants, res = {}, {}
+        for i, ab in enumerate(bindings):
+            if ab.block:
+                assert ab.pw.K == Kin and ab.pw.taps == 1
+                if ab.abits not in quants:
+                    quants[ab.abits] = quant_act_block(x2, geom, ab.abits, None, ln, ldt=ab.Kp // 32)
+                res[i] = gemm_blockq(quants[ab.abits], geom, ab, x.dtype)
+                res[i] = res[i].view(*x.shape[:-1], res[i].shape[-1])
+        rest = [i for i in range(len(bindings)) if i not in res]
+        if rest:
+            for i, y in zip(rest, quant_linear_multi(x, [bindings[i] for i in rest], ln=ln)):
+                res[i] = y
+        return [res[i] for i in range(len(bindings))]
     if any(ab.dynamic for ab in bindings):              # real-time layers of one input (and one bit width) share their row tables
         tables = {}
         for ab in bindings:
@@ -968,7 +1087,8 @@ def quant_conv2d(x: torch.Tensor, ab: ActBinding, kh, kw, stride, pad, norm=None
     xc = x.contiguous(memory_format=torch.channels_last)
     x_store = xc.permute(0, 2, 3, 1)                  # [B,H,W,C] view over the same storage, contiguous
     pre = (*_gn_input(x, x_store, norm), norm[4]) if norm is not None else None
-    ab = _bind_rows(ab, x_store, (B, H, W, C, kh, kw, stride, pad), pre, ups=upsample)      # (real-time: this operand's row tables)
+    if not ab.block:
+        ab = _bind_rows(ab, x_store, (B, H, W, C, kh, kw, stride, pad), pre, ups=upsample)      # (real-time: this operand's row tables)
     Ho = (H + 2 * pad - kh) // stride + 1
     Wo = (W + 2 * pad - kw) // stride + 1
     M = B * Ho * Wo
@@ -981,6 +1101,14 @@ def quant_conv2d(x: torch.Tensor, ab: ActBinding, kh, kw, stride, pad, norm=None
 
     def extra_with(part, conv=None):
         return make_extra(res2, res_div=res_div, gn_partial=part, conv=conv, y2=out2)
+    if ab.block:
+        # real-time block mode: every input pixel (the SOURCE pixel of a folded upsample; a pixel's block parameters do not depend on
+        # the taps that read it) is quantised once, the GEMM gathers the taps
+        geom = (B, H, W, C, kh, kw, stride, pad)
+        q = quant_act_block(x_store, geom, ab.abits, pre, ups=upsample)
+        part = _gn_partial(gn_out, M, N, Ho * Wo, x.device)
+        y = gemm_blockq(q, geom, ab, x.dtype, out=out, extra=extra_with(part), ups=upsample)
+        return _gn_tagged(y, part, B, Ho, Wo, N)
     if kh == 1 and kw == 1 and stride == 1 and pad == 0 and act_fuses(ab, M, C, x.dtype, x2=x_store.reshape(M, C)):
         # a 1x1 convolution is a Linear layer over the pixels: one launch, the GEMM quantises its own rows (dgq_gemm_act_t)
         part = _gn_partial(gn_out, M, N, Ho * Wo, x.device)

@@ -250,6 +250,7 @@ class QuantBasicTransformerBlock(BaseQuantBlock):
             attn.aqtizer_v = UniformAffineQuantizer(**aq_params)
         aq_params_w = dict(aq_params)
         aq_params_w.pop("real_time", None)                     # (the layer-side flag: aqtizer_w keeps t2i_log_quant / t2i_real_time)
+        aq_params_w.pop("real_time_block", None)
         aq_params_w["bits"] = softmax_aq_params["softmax_a_bit"]
         aq_params_w["symmetric"] = False
         aq_params_w["always_zero"] = True

@@ -167,6 +167,17 @@ def row_minmax(row_min: torch.Tensor, row_max: torch.Tensor, level: int):
     return delta, zp
 
 
+#: channels per block of the real-time block mode (``real_time_block``): DGQ_KCHUNK, the depth of one mfma_i32_32x32x32_i8
+REAL_TIME_BLOCK = 32
+
+
+def block_minmax(blk_min: torch.Tensor, blk_max: torch.Tensor, level: int):
+    """``minmax`` of many (row, 32-channel block) cells at once from their fp32 minima / maxima — ``row_minmax`` applied to block
+    extrema, the statement dgq_quant_act_block reproduces bit for bit (real-time block mode).  An all-zero block (a convolution tap
+    outside the image) gives δ = fp32(1e-8), z = 0: code 0, dequantised to exactly 0."""
+    return row_minmax(blk_min, blk_max, level)
+
+
 def group_params_from_ranges(in_min, in_max, out_min, out_max, group_num, mode, level, force_in_channel=None):
     """The host half of ``done_group_num`` (quant_layer.py:338-418) as a pure function of the folded range vectors —
     returns (δ, z, in_channel_wise) in the checkpoint's broadcast shapes.  Arithmetic follows the reference line by
@@ -217,17 +228,27 @@ class UniformAffineQuantizer(nn.Module):
     the quantizer sees gets its own pair from ``Scaler.MINMAX`` applied to that row at run time (dgq_act_row_params; ``row_minmax``
     below is the statement).  The row of a Linear layer is a row of its [M][K] input, the row of a convolution one output position's
     row of the unfolded operand, both behind any folded prologue; an attention-side quantizer (aqtizer_q/k/v) takes one pair per
-    token over batch and heads.  Needs no activation calibration; ``init_from`` is a no-op and the quantizer is always ``init``."""
+    token over batch and heads.  Needs no activation calibration; ``init_from`` is a no-op and the quantizer is always ``init``.
+
+    ``real_time_block=32`` (with ``real_time``): a second granularity — one pair per row AND block of 32 consecutive channels
+    (``block_minmax``), so an outlier sets the step of its own 32 channels only.  A convolution row has, for every tap, the C/32 blocks
+    of that tap's input pixel (a tap outside the image is a block of zeros and contributes exactly 0), so its input is quantised
+    once per pixel (dgq_quant_act_block + dgq_gemm_blockq).  Layers with C % 32 != 0 and the attention-side quantizers keep the
+    per-row / per-token form."""
 
     def __init__(self, bits: int = 8, symmetric: bool = False, channel_wise: bool = False,
                  scaler: Scaler = Scaler.MINMAX, leaf_param: bool = False, always_zero: bool = False,
-                 quant_emb: bool = False, real_time: bool = False) -> None:
+                 quant_emb: bool = False, real_time: bool = False, real_time_block: int = 0) -> None:
         super().__init__()
         if symmetric:
             raise NotImplementedError("symmetric quantizers are not used by the DGQ inference path")
         if real_time and (channel_wise or always_zero or scaler is not Scaler.MINMAX):
             raise ValueError("a real-time activation quantizer is Scaler.MINMAX per row: not channel_wise, not always_zero")
+        if real_time_block not in (0, REAL_TIME_BLOCK) or (real_time_block and not real_time):
+            raise ValueError("real_time_block is 0 (one pair per row) or %d (one pair per row and block of %d consecutive channels), and a "
+                             "granularity of real_time=True" % (REAL_TIME_BLOCK, REAL_TIME_BLOCK))
         self.real_time = bool(real_time)
+        self.real_time_block = int(real_time_block)
         self.level = 2 ** bits
         self.symmetric = symmetric
         self.channel_wise = channel_wise
@@ -367,6 +388,14 @@ class UniformAffineQuantizer(nn.Module):
                 raise NotImplementedError("stand-alone real-time quantizer: [..., C] inputs with C % 4 == 0 (a convolution's rows are "
                                           "those of its unfolded operand: use the QuantLayer)")
             x2d = xc.view(-1, x.shape[-1])
+            if self.real_time_block:
+                # block form: the new quantiser's codes and {δ, β} tables, then a dequantise
+                if x.shape[-1] % self.real_time_block != 0:
+                    raise NotImplementedError("stand-alone real-time block quantizer: [..., C] inputs with C %% %d == 0" % self.real_time_block)
+                codes, table, _rho = ops.quant_act_block(x2d, (x2d.shape[0], 1, 1, x2d.shape[1], 1, 1, 1, 0), self.bits)
+                out = torch.empty_like(xc)
+                ops.dequant_act_block(codes, table, out.view(x2d.shape))
+                return out
             d, z = ops.act_row_params(x2d, (x2d.shape[0], 1, 1, x2d.shape[1], 1, 1, 1, 0), self.bits)
             out = torch.empty_like(xc)
             ops.fakequant_rows(x2d, x2d.shape[0], x2d.shape[1], 1, d, z, 0, self.bits, out=out.view(x2d.shape))
@@ -385,7 +414,8 @@ class UniformAffineQuantizer(nn.Module):
 
     def extra_repr(self) -> str:
         return "level=%d, channel_wise=%s, leaf_param=%s, always_zero=%s%s" % (
-            self.level, self.channel_wise, self.leaf_param, self.always_zero, ", real_time=True" if self.real_time else "")
+            self.level, self.channel_wise, self.leaf_param, self.always_zero,
+            (", real_time=True" + (", real_time_block=%d" % self.real_time_block if self.real_time_block else "")) if self.real_time else "")
 
     def half(self):
         super().half()
@@ -581,7 +611,10 @@ class QuantLayer(nn.Module):
         pw = self.packed_weight()
         if self.aqtizer.real_time:                # no tables, no slots: one natural-order binding, its row tables made per call
             if "real_time" not in self._bindings:
-                self._bindings["real_time"] = ops.DynamicActBinding(pw, self.aqtizer.bits)
+                # block granularity where the input channels split into whole 32-blocks; the per-row mode otherwise
+                blk = self.aqtizer.real_time_block
+                self._bindings["real_time"] = (ops.BlockActBinding(pw, self.aqtizer.bits) if blk and self.in_channels % blk == 0
+                                               else ops.DynamicActBinding(pw, self.aqtizer.bits))
             return self._bindings["real_time"]
         slot = self._slot_ref.slot if self._slot_ref is not None else None
         if slot is not None and slot in self._act_tables:

@@ -44,7 +44,8 @@ extern "C" {
  *   122  round 6: dgq_gemm_extra_t += y2, ldy2; dgq_conv2d_f32w takes y2 / ldy2 / gn_partial
  *   123  dgq_conv2d_wq (the weight-only state from the packed W4 / W8 codes); later, without a new revision because no existing
  *        entry or struct changed (a binding written against 123 keeps working): the real-time per-row activation quantiser tables,
- *        dgq_act_row_params / dgq_act_row_params_batch with their dgq_act_rowparams_out_t */
+ *        dgq_act_row_params / dgq_act_row_params_batch with their dgq_act_rowparams_out_t; the real-time block mode,
+ *        dgq_quant_act_block / dgq_dequant_act_block / dgq_gemm_blockq with dgq_act_block_out_t and dgq_gemm_block_t */
 #define DGQ_ABI_VERSION 123
 int dgq_version(void);
 const char* dgq_last_error(void);
@@ -163,6 +164,24 @@ typedef struct dgq_act_rowparams_out {
 } dgq_act_rowparams_out_t;
 int dgq_act_row_params(const dgq_quant_act_args_t* in, int fold_T, float* ws, size_t ws_floats, float* delta_out, float* zp_out, void* stream);
 int dgq_act_row_params_batch(int n, const dgq_quant_act_args_t* in, const dgq_act_rowparams_out_t* out, void* stream);
+
+/* ---- activations: real-time quantiser per row and 32-channel block (a mode of this library) -----------------------------------------
+ * One (δ, z) per input row AND block of DGQ_KCHUNK = 32 consecutive channels, from Scaler.MINMAX applied to the block at run time
+ * (the arithmetic of dgq_act_row_params on the block's extrema, bit for bit; an all-zero block gives δ = fp32(1e-8), z = 0).  In the
+ * natural (tap, c) K order a 32-chunk of a convolution's unfolded row is 32 channels of one input pixel, so the INPUT is quantised,
+ * once per row / pixel, and dgq_gemm_blockq gathers the taps: `in` is read as by dgq_act_row_params (x, x_dtype, B, H, W, C, bits,
+ * the folded prologue, ups; C % 32 == 0, x 16-byte aligned) but kh, kw, stride, pad only tell a Linear input (1x1: GEGLU /
+ * LayerNorm prologues allowed) from a convolution's.  rows = B·H·W input pixels (a quarter with ups: the source pixels).  ONE launch:
+ *   codes [rows][C] int8, 16-byte aligned: centred codes s = q − 2^(bits−1) in natural channel order;
+ *   table [rows][ldt] pairs of floats {δ, β = δ·(2^(bits−1) − z)}, ldt >= C/32; entries C/32 .. ldt − 1 are written {0, 0} (the chunks
+ *         of a Linear layer's K padding: pass ldt = Kp/32);
+ *   rho   [rows]: Σ_c δ_c·rs_c, rs_c = Σ_{k∈c} s, one fp32 addition per block in ascending block order (deterministic).
+ * dgq_dequant_act_block: y [rows][C] (y_dtype) = δ·(q − z) from such codes and table — the quantizer's stand-alone fake-quant form. */
+typedef struct dgq_act_block_out {
+    int8_t* codes; float* table; int ldt; float* rho;
+} dgq_act_block_out_t;
+int dgq_quant_act_block(const dgq_quant_act_args_t* in, const dgq_act_block_out_t* out, void* stream);
+int dgq_dequant_act_block(const int8_t* codes, const float* table, int ldt, int64_t rows, int C, void* y, int y_dtype, void* stream);
 
 /* GroupNorm of a channels-last tensor x [B][HW][C] as per-(b,c) scale/shift (biased variance, eps as F.group_norm):
  * GN(x) = x·scale + shift.  Replaces norm1/norm2 of QuantResnetBlock2D.forward (quant_block.py:98-119) together with
@@ -349,6 +368,25 @@ typedef struct dgq_gemm_args {
     const dgq_gemm_extra_t* extra;
 } dgq_gemm_args_t;
 int dgq_gemm_wxa8_batch(int n, const dgq_gemm_args_t* args, void* stream);
+
+/* dgq_gemm_blockq: the layer under the real-time block quantiser (dgq_quant_act_block), one launch, no K split, nothing exchanged
+ * between workgroups.  With s the centred codes, qw' / zw the stored weight codes and their zero point, P[m,n,c] = Σ_{k∈c} s·qw' (a
+ * FRESH int32 accumulator per 32-chunk c: no running total, no clear marks), Vc[n,c] = Σ_{k∈c} (qw' − zw):
+ *   y[m,n] = gamma[n] + alpha[n]·( Σ_c ( δ[m,c]·float(P[m,n,c]) + β[m,c]·Vc[n,c] ) − zw[n]·R[m] ),   R[m] = Σ_c δ[m,c]·rs[m,c]
+ * (chunks in ascending order, per chunk first the δ·P term, then the β·Vc term, one fp32 fma each).  Row m = (b·Ho + ho)·Wo + wo, chunk
+ * c = tap·(C/32) + cb reads the 32 code bytes and the table entry cb of input pixel (ho·stride − pad + dh, wo·stride − pad + dw)
+ * (>> 1 with ups); a tap outside the image contributes exactly 0 (δ = β = 0), and R[m] adds the in-image taps' rho in tap order.  A Linear
+ * layer is B = rows, H = W = kh = kw = stride = 1, pad = 0.
+ * Of `g` are read: codes / rowsum (= the quantiser's codes and rho, rowsum_parts 1), M = B·Ho·Wo, Kp (>= kh·kw·C, a multiple of
+ * DGQ_KTILE), wpacked + w_bits (the natural-order image: dgq_pack_w4 layout 1 / dgq_pack_w8 with kperm == NULL), N, alpha, zw, gamma
+ * (= bias), y, y_dtype, ldy and extra (residual / res_div, fq_*, geglu, gn_partial, y2 / ldy2 as for dgq_gemm_wxa8; conv and act must be
+ * NULL, flush_coef and wfrag are ignored); the scale-mode fields are ignored.  vc [N][Kp/32] fp32 (integer-valued, 0 on padding chunks). */
+typedef struct dgq_gemm_block {
+    const float* table; int ldt;      /* dgq_act_block_out_t.table / ldt */
+    const float* vc;
+    int B, H, W, C, kh, kw, stride, pad, ups;
+} dgq_gemm_block_t;
+int dgq_gemm_blockq(const dgq_gemm_args_t* g, const dgq_gemm_block_t* blk, void* stream);
 /* Small tile grids are split along K (deterministic: fp32 partial slabs [S][M][N] in the caller's `workspace`,
  * summed in a fixed order by a second kernel). dgq_gemm_workspace_bytes returns what the preferred split of a
  * shape needs; with workspace == NULL (or too small) fewer / no splits are used — results do not depend on it

@@ -8,6 +8,12 @@ c2 tables, same box, same process — profiles/r08_realtime_act.txt:
   * the row-parameter kernels alone, replayed from a hipGraph: µs and input bytes / time at four SD shapes.
 
     python tools/profile_realtime_act.py --out profiles/r08_realtime_act.txt --stamp "$(git rev-parse --short HEAD)"
+
+--block measures the real-time BLOCK mode (real_time_block=32: dgq_quant_act_block + dgq_gemm_blockq) instead — profiles/r12_realtime_block.txt:
+the two new kernels alone at SD layer shapes (beside the same layer in the row mode), and the step time of the three modes
+(calibrated c2, real-time rows, real-time blocks) in ALTERNATING rounds of one process on one box.
+
+    python tools/profile_realtime_act.py --block --out profiles/r12_realtime_block.txt
 """
 import argparse
 import gc
@@ -64,6 +70,38 @@ def kernel_table(torch, ops, dev, lines):
         lines.append("%-28s %8d %10.2f %12.2f %9.0f" % (name, 1 if geom[4:] == (1, 1, 1, 0) else 2, us, nbytes / 1e6, nbytes / us / 1e3))
 
 
+def block_kernel_table(torch, ops, dev, lines):
+    """dgq_quant_act_block and dgq_gemm_blockq alone at SD 64 x 64 / 32 x 32 layer shapes, beside the whole layer in the row mode"""
+    lines.append("block-mode kernels alone (fp32, W4A8; %d calls per hipGraph replay, median of 5 replays); row mode: the whole layer call" % 20)
+    lines.append("%-34s %12s %12s %12s %14s" % ("layer", "quantiser us", "GEMM us", "block us", "row-mode us"))
+    g = torch.Generator().manual_seed(0)
+    from dgq_amd import synth
+    shapes = [("linear 8192x320 -> 320", (8192, 1, 1, 320, 1, 1, 1, 0), 320), ("linear 8192x320 -> 2560", (8192, 1, 1, 320, 1, 1, 1, 0), 2560),
+              ("linear 8192x1280 -> 320", (8192, 1, 1, 1280, 1, 1, 1, 0), 320), ("linear 2048x640 -> 640", (2048, 1, 1, 640, 1, 1, 1, 0), 640),
+              ("linear 2048x2560 -> 640", (2048, 1, 1, 2560, 1, 1, 1, 0), 640),
+              ("conv3x3 2x320x64x64 -> 320", (2, 64, 64, 320, 3, 3, 1, 1), 320), ("conv3x3 s2 2x320x64x64 -> 320", (2, 64, 64, 320, 3, 3, 2, 1), 320),
+              ("conv3x3 2x640x32x32 -> 640", (2, 32, 32, 640, 3, 3, 1, 1), 640), ("conv3x3 2x1280x32x32 -> 640", (2, 32, 32, 1280, 3, 3, 1, 1), 640)]
+    for name, geom, N in shapes:
+        B, H, W, C, kh, kw, stride, pad = geom
+        taps = kh * kw
+        w = torch.randn(N, C * taps, generator=g) * (C * taps) ** -0.5
+        wd, wz = synth.channel_minmax(w, 4)
+        pw = ops.PackedWeight(w.to(dev), wd.to(dev), wz.to(dev), None, torch.zeros(N).to(dev), 4, C, taps)
+        blk, row = ops.BlockActBinding(pw, 8), ops.DynamicActBinding(pw, 8)
+        x = (torch.randn(B, H, W, C, generator=g) * 1.3 + 0.2).to(dev)
+        ldt = blk.Kp // 32 if taps == 1 else C // 32
+        q = ops.quant_act_block(x, geom, 8, ldt=ldt)
+        us_q = replayed_us(torch, lambda: ops.quant_act_block(x, geom, 8, ldt=ldt))
+        us_g = replayed_us(torch, lambda: ops.gemm_blockq(q, geom, blk, torch.float32))
+        if taps == 1:
+            x2 = x.view(B, C)
+            us_r = replayed_us(torch, lambda: ops.quant_linear(x2, row))
+        else:
+            xn = x.permute(0, 3, 1, 2)
+            us_r = replayed_us(torch, lambda: ops.quant_conv2d(xn, row, kh, kw, stride, pad, gn_out=False))
+        lines.append("%-34s %12.2f %12.2f %12.2f %14.2f" % (name, us_q, us_g, us_q + us_g, us_r))
+
+
 def build_model(torch, mode, steps_cfg, slots, batch, dev):
     """(qnn, seconds until ready, GB allocated on the device once ready)"""
     import bench
@@ -89,6 +127,8 @@ def build_model(torch, mode, steps_cfg, slots, batch, dev):
         unet.load_state_dict(synth.state_dict_from_ckpt(path))
         wq, aq, sm = quant_params(Scaler, 4, 8, True, cfg["log"], cfg["rt"], cfg["sp"])
         aq["real_time"] = True
+        if mode == "real_time_block":
+            aq["real_time_block"] = 32
         qnn = get_qmodel("sd", types.SimpleNamespace(unet=unet), path, wq, True, aq, sm, False, steps_cfg, False, device=dev)
         qnn = qnn.float().to(dev)
         qnn.disable_out_quantization()
@@ -142,6 +182,65 @@ def time_model(torch, ops, qnn, timesteps, warmup, windows, dev):
     return statistics.median(secs) * 1e3, len(calls), by, after_step
 
 
+def block_step_table(torch, ops, args, dev, lines):
+    """the three modes' step times in alternating rounds of one process: every model is built and captured first, then each round
+    times calibrated, rows, blocks in turn"""
+    from dgq_amd import synth
+    from dgq_amd.runtime import DDIMScheduler
+    sched = DDIMScheduler(50).timesteps
+    n = args.steps + args.warmup
+    timesteps = [int(sched[i % min(n, len(sched))]) for i in range(n)]
+    slots = sorted({(1000 - t) // 20 for t in timesteps})
+    sch = DDIMScheduler(50)
+    lat = synth.named_randn("latent", (1, 4, 64, 64), 1).to(dev)
+    ctx = synth.named_randn("ctx", (2, 77, 768), 100).to(dev)
+    modes = (("calibrated", "calibrated c2 (g16, %d time-aware slots)" % len(slots)), ("real_time", "real-time rows (weight-only ckpt)"),
+             ("real_time_block", "real-time blocks of 32 (weight-only ckpt)"))
+    models, info = {}, {}
+    for mode, _label in modes:
+        qnn, ready, gb = build_model(torch, mode, 50, slots, 2, dev)
+
+        def one_step(x, t, qnn=qnn):
+            eps = qnn(torch.cat([x, x], dim=0), t, ctx)[0]
+            return sch.step_guided(eps, t, x, 7.5) if hasattr(sch, "step_guided") else sch.step(eps.chunk(2)[0] + 7.5 * (eps.chunk(2)[1] - eps.chunk(2)[0]), t, x)
+        calls, orig = [], ops._lib_call
+        with torch.no_grad():
+            one_step(lat, timesteps[0])
+            ops._lib_call = lambda name, *a: (calls.append(name), orig(name, *a))[1]
+            try:
+                one_step(lat, timesteps[0])
+            finally:
+                ops._lib_call = orig
+            qnn.enable_graphs(True)
+            for t in sorted(set(timesteps), reverse=True):
+                one_step(lat, t)
+        by = {}
+        for c in calls:
+            by[c] = by.get(c, 0) + 1
+        models[mode], info[mode] = one_step, (len(calls), by, ready, gb, [])
+    with torch.no_grad():
+        for _ in range(args.windows):
+            for mode, _label in modes:
+                x = lat
+                for t in timesteps[:args.warmup]:
+                    x = models[mode](x, t)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for t in timesteps[args.warmup:]:
+                    x = models[mode](x, t)
+                torch.cuda.synchronize()
+                info[mode][4].append((time.perf_counter() - t0) / args.steps * 1e3)
+                assert torch.isfinite(x).all()
+    lines += ["", "SD1.4-size synthetic model, 512^2 (64x64 latents), CFG pair, fp32, W4A8; hipGraph replay, %d timed steps behind %d warm-up steps per window,"
+              % (args.steps, args.warmup), "%d ALTERNATING rounds (calibrated, rows, blocks, calibrated, ...) in one process on one box" % args.windows,
+              "%-44s %10s %10s %10s %12s %14s" % ("mode", "median ms", "min ms", "max ms", "entry calls", "GB after load")]
+    for mode, label in modes:
+        ncalls, by, ready, gb, ms = info[mode]
+        lines.append("%-44s %10.3f %10.3f %10.3f %12d %14.2f" % (label, statistics.median(ms), min(ms), max(ms), ncalls, gb))
+    lines += ["", "entry calls = calls of libdgq_hip.so entries in one eager step (a call is one to three kernel launches), by entry:"]
+    lines += ["%s: %s" % (mode, ", ".join("%s %d" % kv for kv in sorted(info[mode][1].items(), key=lambda kv: -kv[1]))) for mode, _ in modes]
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default="profiles/r08_realtime_act.txt")
@@ -150,6 +249,7 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--kernels-only", action="store_true")
+    ap.add_argument("--block", action="store_true", help="measure the real-time block mode (see the head of this file)")
     args = ap.parse_args(argv)
     import torch
     from dgq_amd import _lib, ops
@@ -157,6 +257,18 @@ def main(argv=None):
     _lib.require_gpu()
     torch.set_num_threads(min(torch.get_num_threads(), 16))
     dev = torch.device("cuda", 0)
+    if args.block:
+        lines = ["real-time block activation mode (real_time_block=32) — tools/profile_realtime_act.py --block",
+                 "commit %s; %s; torch %s; ABI %d" % (args.stamp or stamp_default(), torch.cuda.get_device_name(0), torch.__version__, _lib.ABI_VERSION), ""]
+        block_kernel_table(torch, ops, dev, lines)
+        if not args.kernels_only:
+            block_step_table(torch, ops, args, dev, lines)
+        text = "\n".join(lines) + "\n"
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text)
+        print(text)
+        return 0
     lines = ["real-time per-row activation mode vs calibrated c2 tables — tools/profile_realtime_act.py",
              "commit %s; %s; torch %s; ABI %d" % (args.stamp or stamp_default(), torch.cuda.get_device_name(0), torch.__version__, _lib.ABI_VERSION), ""]
     kernel_table(torch, ops, dev, lines)
