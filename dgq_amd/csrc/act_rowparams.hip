@@ -21,13 +21,7 @@
 #define DGQ_RP_BATCH 4
 
 struct RowParamsProblem {
-    const void* x;
-    int rows;                 // rows of the rows kernel: B·Hs·Ws source pixels (Linear: M)
-    int rows_per_image;       // Hs·Ws (pre_scale / pre_shift are [B][C])
-    int C, ldc;
-    const float* pre_scale; const float* pre_shift; int pre_act;
-    const float* ln_gamma; const float* ln_beta; float ln_eps;
-    float levels;             // 2^b − 1
+    QuantRowInput in;         // the rows of the rows kernel
     float* ext;               // [rows][2] (min(row min, 0), max(row max, 0)), or NULL: the rows kernel writes δ / z itself
     float* delta; float* zp;
     int entries;              // table entries the finish kernel writes: M, or fold_T
@@ -41,32 +35,28 @@ struct RowParamsBatch {
 template <typename TIn>
 __global__ __launch_bounds__(256) void rowparams_rows_kernel(RowParamsBatch bt) {
     const RowParamsProblem& p = bt.p[blockIdx.y];
+    const QuantRowInput& in = p.in;
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= p.rows) return;                              // whole wave leaves; no barriers below
-    const TIn* xr = reinterpret_cast<const TIn*>(p.x) + (int64_t)row * p.ldc;
-    const int b = row / p.rows_per_image;
-    const float* pre_sc = p.pre_scale ? p.pre_scale + (int64_t)b * p.C : nullptr;
-    const float* pre_sh = p.pre_shift ? p.pre_shift + (int64_t)b * p.C : nullptr;
-    float ln_mu = 0.0f, ln_rstd = 1.0f;
-    if (p.ln_gamma) row_layernorm_stats<TIn>(xr, p.C, p.ln_eps, lane, ln_mu, ln_rstd);
+    if (row >= in.rows) return;                             // whole wave leaves; no barriers below
+    const QuantRowSource<TIn> s = quant_row_source<TIn>(in, row, lane);
     float mn = 0.0f, mx = 0.0f;                             // MINMAX includes 0 in the range
     // four 16-byte loads per lane in flight; every load goes out unconditionally at a clamped address (C % 4 == 0, C >= 4) and a
     // vector past the end is computed and discarded
-    for (int c0 = lane * 4; c0 < p.C; c0 += 1024) {
+    for (int c0 = lane * 4; c0 < in.C; c0 += 1024) {
         float v[4][4], g[4][4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const int c = min(c0 + 256 * u, p.C - 4);
-            load4<TIn>(xr + c, v[u]);
-            if (p.pre_act == 2) load4<TIn>(xr + p.C + c, g[u]);
+            const int c = min(c0 + 256 * u, in.C - 4);
+            load4<TIn>(s.xr + c, v[u]);
+            if (in.pre_act == 2) load4<TIn>(s.xr + in.C + c, g[u]);
             else g[u][0] = g[u][1] = g[u][2] = g[u][3] = 0.0f;
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const int c = min(c0 + 256 * u, p.C - 4);
-            dgq_prologue4(v[u], c, pre_sc, pre_sh, p.ln_gamma, p.ln_beta, ln_mu, ln_rstd, p.pre_act, g[u]);
-            if (c0 + 256 * u < p.C) {
+            const int c = min(c0 + 256 * u, in.C - 4);
+            dgq_prologue4(v[u], c, s.pre_sc, s.pre_sh, in.ln_gamma, in.ln_beta, s.ln_mu, s.ln_rstd, in.pre_act, g[u]);
+            if (c0 + 256 * u < in.C) {
                 mn = fminf(mn, fminf(fminf(v[u][0], v[u][1]), fminf(v[u][2], v[u][3])));
                 mx = fmaxf(mx, fmaxf(fmaxf(v[u][0], v[u][1]), fmaxf(v[u][2], v[u][3])));
             }
@@ -82,7 +72,7 @@ __global__ __launch_bounds__(256) void rowparams_rows_kernel(RowParamsBatch bt) 
             *reinterpret_cast<float2*>(p.ext + 2 * (int64_t)row) = make_float2(mn, mx);
         } else {
             float d, z;
-            minmax_params(mn, mx, p.levels, d, z);
+            minmax_params(mn, mx, p.in.levels, d, z);
             p.delta[row] = d;
             p.zp[row] = z;
         }
@@ -96,7 +86,7 @@ __global__ __launch_bounds__(256) void rowparams_finish_kernel(RowParamsBatch bt
     const float2* ext = reinterpret_cast<const float2*>(p.ext);
     float mn = 0.0f, mx = 0.0f;
     if (p.fold_T > 0) {
-        for (int r = m; r < p.rows; r += p.fold_T) {
+        for (int r = m; r < p.in.rows; r += p.fold_T) {
             const float2 e = ext[r];
             mn = fminf(mn, e.x);
             mx = fmaxf(mx, e.y);
@@ -120,41 +110,25 @@ __global__ __launch_bounds__(256) void rowparams_finish_kernel(RowParamsBatch bt
         }
     }
     float d, z;
-    minmax_params(mn, mx, p.levels, d, z);
+    minmax_params(mn, mx, p.in.levels, d, z);
     p.delta[m] = d;
     p.zp[m] = z;
 }
 
 static int fill_row_params(const dgq_quant_act_args_t& a, const dgq_act_rowparams_out_t& o, RowParamsProblem& p) {
-    DGQ_CHECK_ARG(a.x && o.delta && o.zp, "dgq_act_row_params: null pointer");
-    DGQ_CHECK_ARG(((uintptr_t)a.x & 15) == 0, "dgq_act_row_params: x must be 16-byte aligned");
-    DGQ_CHECK_ARG(a.B > 0 && a.H > 0 && a.W > 0 && a.C > 0 && a.kh > 0 && a.kw > 0 && a.stride > 0 && a.pad >= 0,
-                  "dgq_act_row_params: bad geometry");
-    DGQ_CHECK_ARG(a.kh <= 0x7F && a.kw <= 0xFF, "dgq_act_row_params: kernel size out of range");
-    DGQ_CHECK_ARG(a.C % 4 == 0, "dgq_act_row_params: C=%d must be a multiple of 4", a.C);
-    DGQ_CHECK_ARG(a.bits >= 2 && a.bits <= 8, "dgq_act_row_params: bits=%d", a.bits);
-    DGQ_CHECK_ARG((a.pre_scale == nullptr) == (a.pre_shift == nullptr) && a.pre_act >= 0 && a.pre_act <= 2, "dgq_act_row_params: bad prologue");
-    DGQ_CHECK_ARG(a.pre_act != 2 || (a.kh == 1 && a.kw == 1 && !a.pre_scale), "dgq_act_row_params: GEGLU prologue is for Linear inputs");
-    DGQ_CHECK_ARG((a.ln_gamma == nullptr) == (a.ln_beta == nullptr), "dgq_act_row_params: LayerNorm prologue needs gamma and beta");
-    DGQ_CHECK_ARG(!a.ln_gamma || (a.kh == 1 && a.kw == 1 && !a.pre_scale && a.pre_act == 0 && a.C <= DGQ_LN_MAX_C && a.ln_eps > 0.0f),
-                  "dgq_act_row_params: LayerNorm prologue is for Linear inputs (1x1, C <= 2048, no other prologue)");
-    const int ups = a.ups ? 1 : 0;
-    DGQ_CHECK_ARG(!ups || (a.H % 2 == 0 && a.W % 2 == 0 && a.kh * a.kw > 1), "dgq_act_row_params: ups needs even H, W and a convolution");
-    const int Ho = (a.H + 2 * a.pad - a.kh) / a.stride + 1, Wo = (a.W + 2 * a.pad - a.kw) / a.stride + 1;
-    DGQ_CHECK_ARG(Ho > 0 && Wo > 0, "dgq_act_row_params: empty output");
-    const int Hs = a.H >> ups, Ws = a.W >> ups;
-    const int64_t rows = (int64_t)a.B * Hs * Ws, M = (int64_t)a.B * Ho * Wo;
-    DGQ_CHECK_ARG(rows < (1LL << 30) && M < (1LL << 30), "dgq_act_row_params: too many rows");
+    DGQ_CHECK_ARG(o.delta && o.zp, "dgq_act_row_params: null pointer");
+    int Ho, Wo;
+    const int rc = dgq_check_quant_input(a, "dgq_act_row_params", {4, true, true}, p.in, Ho, Wo);
+    if (rc != DGQ_OK) return rc;
+    const int ups = a.ups ? 1 : 0, Hs = a.H >> ups, Ws = a.W >> ups;
+    const int64_t rows = p.in.rows, M = (int64_t)a.B * Ho * Wo;
+    DGQ_CHECK_ARG(M < (1LL << 30), "dgq_act_row_params: too many rows");
     const bool plain = a.kh == 1 && a.kw == 1 && a.stride == 1 && a.pad == 0;       // a row of the table is a row of the input
     DGQ_CHECK_ARG(o.fold_T >= 0 && (o.fold_T == 0 || (plain && M % o.fold_T == 0)), "dgq_act_row_params: fold_T=%d needs a Linear input "
                   "whose row count (%lld) it divides", o.fold_T, (long long)M);
     const bool two = !plain || o.fold_T > 0;
     DGQ_CHECK_ARG(!two || (o.ws && ((uintptr_t)o.ws & 7) == 0 && o.ws_floats >= (size_t)(2 * rows)),
                   "dgq_act_row_params: workspace of %lld floats (8-byte aligned) needed, %zu given", (long long)(2 * rows), o.ws_floats);
-    p.x = a.x; p.rows = (int)rows; p.rows_per_image = Hs * Ws; p.C = a.C; p.ldc = a.pre_act == 2 ? 2 * a.C : a.C;
-    p.pre_scale = a.pre_scale; p.pre_shift = a.pre_shift; p.pre_act = a.pre_act;
-    p.ln_gamma = a.ln_gamma; p.ln_beta = a.ln_beta; p.ln_eps = a.ln_eps;
-    p.levels = (float)((1 << a.bits) - 1);
     p.ext = two ? o.ws : nullptr;
     p.delta = o.delta; p.zp = o.zp;
     p.entries = o.fold_T > 0 ? o.fold_T : (int)M;
@@ -173,7 +147,7 @@ extern "C" int dgq_act_row_params_batch(int n, const dgq_quant_act_args_t* in, c
         const int rc = fill_row_params(in[i], out[i], bt.p[i]);
         if (rc != DGQ_OK) return rc;
         DGQ_CHECK_ARG(in[i].x_dtype == in[0].x_dtype, "dgq_act_row_params_batch: problem %d differs from problem 0 in dtype", i);
-        rows = std::max(rows, bt.p[i].rows);
+        rows = std::max(rows, bt.p[i].in.rows);
         const bool two = bt.p[i].ext != nullptr;
         any_two = any_two || two;
         all_two = all_two && two;
@@ -183,12 +157,7 @@ extern "C" int dgq_act_row_params_batch(int n, const dgq_quant_act_args_t* in, c
     for (int i = n; i < DGQ_RP_BATCH; ++i) bt.p[i] = bt.p[0];
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((rows + 3) / 4, n), block(256);
-    switch (in[0].x_dtype) {
-        case DGQ_F32: hipLaunchKernelGGL((rowparams_rows_kernel<float>), grid, block, 0, st, bt); break;
-        case DGQ_F16: hipLaunchKernelGGL((rowparams_rows_kernel<__half>), grid, block, 0, st, bt); break;
-        case DGQ_BF16: hipLaunchKernelGGL((rowparams_rows_kernel<__hip_bfloat16>), grid, block, 0, st, bt); break;
-        default: dgq_set_error("dgq_act_row_params: unknown dtype %d", in[0].x_dtype); return DGQ_EINVAL;
-    }
+    DGQ_QUANT_DTYPE_SWITCH(in[0].x_dtype, "dgq_act_row_params", hipLaunchKernelGGL((rowparams_rows_kernel<TIn>), grid, block, 0, st, bt))
     if (any_two) hipLaunchKernelGGL(rowparams_finish_kernel, dim3((entries + 255) / 256, n), dim3(256), 0, st, bt);
     return dgq_launch_status("dgq_act_row_params");
 }

@@ -90,6 +90,9 @@ __device__ __forceinline__ float dgq_silu(float x) {
     return x * q;
 }
 
+// x·gelu(g), gelu by erf as F.gelu's default (FeedForward's GEGLU: the GEMM epilogue and the quantisers' folded prologue, diffusers_rewrite/sd.py:210-222)
+__device__ __forceinline__ float dgq_geglu(float a, float g) { return a * (0.5f * g * (1.0f + erff(g * 0.70710678118654752f))); }
+
 // The same code, bit for bit, at the cost of a multiply: with inv = v_rcp_f32(δ) (1 ulp), t = fl(x·inv) differs from the
 // real quotient q by < |q|·1.8e-7, and the correctly rounded fl(q) by < |q|·0.6e-7; so whenever t is farther than
 // |t|·4e-7 from every half-integer, rint(t) == rint(fl(x/δ)).  Only values inside that band (probability ~1e-4 per

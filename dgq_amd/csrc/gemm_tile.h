@@ -78,9 +78,6 @@ __device__ __forceinline__ float dgq_epilogue(const GemmParams& p, float acc, in
     return dgq_dequant<false>(acc, 1.0f, rs, 0.0f, al, zw, ga, vn);
 }
 
-// x·gelu(g), gelu by erf as F.gelu's default (FeedForward's GEGLU, diffusers_rewrite/sd.py:210-222)
-__device__ __forceinline__ float dgq_geglu(float a, float g) { return a * (0.5f * g * (1.0f + erff(g * 0.70710678118654752f))); }
-
 // LDS ring: NST stages (template parameter; 3 is what ships — see launch_ring).
 constexpr int gemm_stage_bytes(int wbits, int bm, int bn) { return bm * BK + bn * (wbits == 4 ? BK / 2 : BK); }
 // waves per SIMD the LDS ring of a tile shape allows (ring + tables), capped at 5 blocks per CU: the register budget follows

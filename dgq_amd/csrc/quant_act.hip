@@ -51,8 +51,6 @@ struct QuantActBatch {
 // prologue once, then quantises and stores it NSH times, instead of NSH workgroups each reading the row again.
 #define DGQ_QA_SHARE 4
 
-
-
 // One wave per output row; each lane owns 4 consecutive kp per 256-wide step (one packed dword), so that the
 // table read (int4), the gathered loads (lane stride 16 B within a (group, tap) run) and the code store (256 B per
 // wave instruction) are all coalesced.  The 4 kp of a lane share one 32-wide chunk, hence one (δ, z).
@@ -394,6 +392,8 @@ __global__ __launch_bounds__(256) void quant_act_staged_kernel(QuantActBatch bt)
 // row) for large M; 1 (the four waves take the taps round-robin and share the row image) where M alone cannot fill the chip.
 // (round 4) RPB == 1 runs NWV = 8 or 16 waves per row: with four, a wave walked up to 3 taps x C/256 dependent load rounds (16.6 us for
 // 128 x 11904 codes against 6.0 us for the per-M form of the same layer); the (tap, 256-channel step) units are dealt round-robin instead.
+// LDS bytes in front of the row image(s): δ, 1/δ, z per 32-chunk and 16 per-wave partial sums, 16-byte aligned
+__host__ __device__ constexpr int quant_scatter_table_bytes(int Kp) { return ((3 * (Kp >> 5) + 16) * 4 + 15) & ~15; }
 template <typename TIn, int RPB, int NWV = 4>
 __global__ __launch_bounds__(64 * NWV) void quant_act_scatter_kernel(QuantActBatch bt) {
     static_assert(RPB == 1 || NWV == 4 || NWV == 8, "four rows per block: one or two waves each");
@@ -409,7 +409,7 @@ __global__ __launch_bounds__(64 * NWV) void quant_act_scatter_kernel(QuantActBat
     float* tinv = tdelta + nch;
     float* tzp = tinv + nch;
     float* psum = tzp + nch;                                 // [16] per-wave partial row sums (RPB == 1)
-    uint8_t* images = sc_smem + (((3 * nch + 16) * 4 + 15) & ~15);
+    uint8_t* images = sc_smem + quant_scatter_table_bytes(p.Kp);
     for (int i = tid; i < nch; i += NT_) {
         const float d = p.delta[i];
         tdelta[i] = d; tinv[i] = dgq_rcp(d); tzp[i] = p.zp[i];
@@ -442,45 +442,45 @@ __global__ __launch_bounds__(64 * NWV) void quant_act_scatter_kernel(QuantActBat
             const bool inb = hi >= 0 && hi < p.H && wi >= 0 && wi < p.W;     // wave-uniform
             const TIn* src = img + ((int64_t)(hi >> us) * Ws + (wi >> us)) * p.ldc;
             const int32_t* kd = p.kdst + tap * p.C;
-                float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (inb) {
-                    load4<TIn>(src + c, v);
-                    if (pre_sc) {
-                        const float4 sc = *reinterpret_cast<const float4*>(pre_sc + c);
-                        const float4 sh = *reinterpret_cast<const float4*>(pre_sh + c);
-                        v[0] = v[0] * sc.x + sh.x; v[1] = v[1] * sc.y + sh.y; v[2] = v[2] * sc.z + sh.z; v[3] = v[3] * sc.w + sh.w;
-                    }
-                    if (p.ln_gamma) {
-                        const float4 ga = *reinterpret_cast<const float4*>(p.ln_gamma + c);
-                        const float4 be = *reinterpret_cast<const float4*>(p.ln_beta + c);
-                        v[0] = (v[0] - ln_mu) * ln_rstd * ga.x + be.x; v[1] = (v[1] - ln_mu) * ln_rstd * ga.y + be.y;
-                        v[2] = (v[2] - ln_mu) * ln_rstd * ga.z + be.z; v[3] = (v[3] - ln_mu) * ln_rstd * ga.w + be.w;
-                    }
-                    if (p.pre_act == 1) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] = dgq_silu(v[j]);
-                    } else if (p.pre_act == 2) {
-                        float g[4];
-                        load4<TIn>(src + p.C + c, g);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] = v[j] * (0.5f * g[j] * (1.0f + erff(g[j] * 0.70710678118654752f)));
-                    }
+            float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (inb) {
+                load4<TIn>(src + c, v);
+                if (pre_sc) {
+                    const float4 sc = *reinterpret_cast<const float4*>(pre_sc + c);
+                    const float4 sh = *reinterpret_cast<const float4*>(pre_sh + c);
+                    v[0] = v[0] * sc.x + sh.x; v[1] = v[1] * sc.y + sh.y; v[2] = v[2] * sc.z + sh.z; v[3] = v[3] * sc.w + sh.w;
                 }
-                const int4 d4 = *reinterpret_cast<const int4*>(kd + c);
-                const int dst[4] = {d4.x, d4.y, d4.z, d4.w};
-                float dd[4], di[4], dz[4], qv[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int ch = dst[j] >> 5;
-                    dd[j] = tdelta[ch]; di[j] = tinv[ch]; dz[j] = tzp[ch];
+                if (p.ln_gamma) {
+                    const float4 ga = *reinterpret_cast<const float4*>(p.ln_gamma + c);
+                    const float4 be = *reinterpret_cast<const float4*>(p.ln_beta + c);
+                    v[0] = (v[0] - ln_mu) * ln_rstd * ga.x + be.x; v[1] = (v[1] - ln_mu) * ln_rstd * ga.y + be.y;
+                    v[2] = (v[2] - ln_mu) * ln_rstd * ga.z + be.z; v[3] = (v[3] - ln_mu) * ln_rstd * ga.w + be.w;
                 }
-                dgq_affine_code4_fast(v, dd, di, dz, p.qmax, qv);
+                if (p.pre_act == 1) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float sc = qv[j] - p.offset;
-                    image[dst[j]] = (uint8_t)(int)sc;
-                    partial += dd[j] * sc;
+                    for (int j = 0; j < 4; ++j) v[j] = dgq_silu(v[j]);
+                } else if (p.pre_act == 2) {
+                    float g[4];
+                    load4<TIn>(src + p.C + c, g);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] = v[j] * (0.5f * g[j] * (1.0f + erff(g[j] * 0.70710678118654752f)));
                 }
+            }
+            const int4 d4 = *reinterpret_cast<const int4*>(kd + c);
+            const int dst[4] = {d4.x, d4.y, d4.z, d4.w};
+            float dd[4], di[4], dz[4], qv[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int ch = dst[j] >> 5;
+                dd[j] = tdelta[ch]; di[j] = tinv[ch]; dz[j] = tzp[ch];
+            }
+            dgq_affine_code4_fast(v, dd, di, dz, p.qmax, qv);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float sc = qv[j] - p.offset;
+                image[dst[j]] = (uint8_t)(int)sc;
+                partial += dd[j] * sc;
+            }
         };
         if constexpr (WPR == 1) {                            // one wave per row: taps in order, channel steps inside (loads of a tap overlap)
             for (int tap = 0; tap < taps; ++tap)
@@ -636,9 +636,11 @@ __global__ __launch_bounds__(64 * NW) void quant_act_conv_kernel(QuantActBatch b
 // tile of the block-staged conv path for a geometry: the largest of 4x8 / 4x4 / 2x4 output positions whose input patch fits
 // the LDS (two workgroups per CU for the first, one for the others); 0 = none (the per-row paths take the layer)
 struct ConvTile { int id, th, tw, pw; size_t lds; };
+// bytes of the tile rule's tables behind the patch: 16-bit indices and 8 bytes per 32-chunk (conv_lds_bytes adds what the records take on top)
+static size_t conv_table_bytes(int Kp) { return (size_t)Kp * 2 + (size_t)(Kp >> 5) * 8 + 64; }
 static ConvTile conv_tile(int C, int kh, int kw, int stride, int Kp) {
     const int cand[3][2] = {{4, 8}, {4, 4}, {2, 4}};
-    const size_t tables = (size_t)Kp * 2 + (size_t)(Kp >> 5) * 8 + 64;
+    const size_t tables = conv_table_bytes(Kp);
     ConvTile fit = {0, 0, 0, 0, 0};
     for (int i = 0; i < 3; ++i) {
         const int th = cand[i][0], tw = cand[i][1];
@@ -662,7 +664,7 @@ static ConvTile conv_tile_geo(const QuantActParams& p) {
     ConvTile t = conv_tile(p.C, p.kh, p.kw, p.stride, p.Kp);
     if (t.id == 2 && conv_tiles(p, t) < 256) {
         const int ph = (2 - 1) * p.stride + p.kh;
-        ConvTile h = {3, 2, 4, t.pw, (size_t)ph * t.pw * p.C * sizeof(float) + ((size_t)p.Kp * 2 + (size_t)(p.Kp >> 5) * 8 + 64)};
+        ConvTile h = {3, 2, 4, t.pw, (size_t)ph * t.pw * p.C * sizeof(float) + conv_table_bytes(p.Kp)};
         if (conv_tiles(p, h) >= 256) return h;
     }
     return t;
@@ -698,34 +700,30 @@ static int quant_act_variant(const QuantActParams& p, bool table) {
     // evaluates the quantiser for every PACKED position, padding included; the scatter path evaluates it once per SOURCE
     // element (K instead of Kp codes, 16-byte coalesced reads with the LayerNorm / GEGLU prologue applied on the way) and
     // drops the byte into the row image in LDS.  Taken where the padding is at least a quarter of K.
-    {
-        const size_t tab_b = (((size_t)3 * (p.Kp >> 5) + 16) * 4 + 15) & ~(size_t)15;
-        if (table && p.kdst && taps_ == 1 && p.C % 4 == 0 && ks == 1 && (!p.ln_gamma || p.C <= DGQ_LN_MAX_C) &&
-            tab_b + 4 * (size_t)p.Kp <= 150 * 1024 && 4 * p.Kp >= 5 * p.K)
-            return 3;
-    }
+    const size_t sc_tab = (size_t)quant_scatter_table_bytes(p.Kp);
+    if (table && p.kdst && taps_ == 1 && p.C % 4 == 0 && ks == 1 && (!p.ln_gamma || p.C <= DGQ_LN_MAX_C) &&
+        sc_tab + 4 * (size_t)p.Kp <= 150 * 1024 && 4 * p.Kp >= 5 * p.K)
+        return 3;
     // convolutions whose input patch fits the LDS: the block-staged path
-    {
-        if (p.kpat && taps_ > 1 && p.C % 4 == 0 && ks == 1 && p.pre_act != 2 && !p.ln_gamma &&
-            conv_block_pays(p, conv_tile_geo(p)))
-            return 5;
-    }
+    if (p.kpat && taps_ > 1 && p.C % 4 == 0 && ks == 1 && p.pre_act != 2 && !p.ln_gamma && conv_block_pays(p, conv_tile_geo(p))) return 5;
     const bool stage_conv = taps_ > 1 && p.pre_act != 2 && !p.ln_gamma && ks == 1;
     const bool stage_lin = taps_ == 1 && (!p.ln_gamma || p.C <= DGQ_LN_MAX_C);
     if (table && p.klds && p.C % 4 == 0 && strip_bytes <= 16 * 1024 && (stage_conv || stage_lin)) return 0;
     // scatter path: per-K table, more than one tap, the whole row in one wave/block (no K split), no LN / GEGLU prologue
-    const size_t sc_tab = (((size_t)3 * (p.Kp >> 5) + 16) * 4 + 15) & ~(size_t)15;
     if (table && p.kdst && taps_ > 1 && p.C % 4 == 0 && ks == 1 && p.pre_act != 2 && !p.ln_gamma && sc_tab + (size_t)p.Kp <= 150 * 1024)
         return (p.M >= 4096 && sc_tab + 4 * (size_t)p.Kp <= 150 * 1024) ? 3 : 4;     // (2048 rows x 17536: 79 us with one wave per row, see below)
     // per-K Linear inputs too wide for a staged strip (K > 4096: SDXL's ff.net.2 at 5120): the multi-wave scatter form instead of the
     // global gather (one L1 access per code)
-    {
-        const size_t tab_b = (((size_t)3 * (p.Kp >> 5) + 16) * 4 + 15) & ~(size_t)15;
-        if (table && p.kdst && taps_ == 1 && p.C % 4 == 0 && ks == 1 && !p.ln_gamma && p.pre_act != 2 && tab_b + (size_t)p.Kp <= 150 * 1024)
-            return 4;
-    }
+    if (table && p.kdst && taps_ == 1 && p.C % 4 == 0 && ks == 1 && !p.ln_gamma && p.pre_act != 2 && sc_tab + (size_t)p.Kp <= 150 * 1024) return 4;
     return table ? 1 : 2;
 }
+
+// one launch with PM bound to the scale mode: `...` names the kernel instantiation through PM
+#define DGQ_QA_PER_M(per_m, ...)                             \
+    do {                                                     \
+        if (per_m) { constexpr bool PM = true; __VA_ARGS__; } \
+        else { constexpr bool PM = false; __VA_ARGS__; }     \
+    } while (0)
 
 // all n problems: same variant, same per_m, same M (checked by the caller)
 template <typename TIn>
@@ -740,7 +738,7 @@ static void launch_quant_act(const QuantActBatch& bt, int n, int variant, bool p
     }
     if (variant == 5) {
         const ConvTile t = conv_tile_geo(p0);
-        const int tiles = p0.B * ((p0.Ho + t.th - 1) / t.th) * ((p0.Wo + t.tw - 1) / t.tw);
+        const int tiles = (int)conv_tiles(p0, t);
         size_t lds5 = 0;
         for (int i = 0; i < n; ++i) lds5 = std::max(lds5, conv_lds_bytes(t, bt.p[i].Kp));
         static std::atomic<bool> attr5[64];                  // all six instantiations of this dtype, once
@@ -750,29 +748,22 @@ static void launch_quant_act(const QuantActBatch& bt, int n, int variant, bool p
                                       {&quant_act_conv_kernel<TIn, false, 4, 4, 16>, DGQ_QA_CONV_LDS_MAX},
                                       {&quant_act_conv_kernel<TIn, true, 2, 4, 16>, DGQ_QA_CONV_LDS_MAX},
                                       {&quant_act_conv_kernel<TIn, false, 2, 4, 16>, DGQ_QA_CONV_LDS_MAX}});
-#define DGQ_QA_CONV(PM, TH_, TW_) hipLaunchKernelGGL((quant_act_conv_kernel<TIn, PM, TH_, TW_, 8>), dim3(tiles, 1, n), dim3(512), lds5, st, bt)
-        if (t.id == 1) { if (per_m) DGQ_QA_CONV(true, 4, 8); else DGQ_QA_CONV(false, 4, 8); }
-        else if (t.id == 2) {
-            // 16 positions per tile: one wave per output position (16 waves) instead of two positions per wave — the gather / quantise phase is a
-            // chain of dependent LDS reads per 1024 codes, and twice the waves hide twice the latency (same lanes, same order per row:
-            // bit-identical; step +0.3-0.5 % same box)
-            if (per_m) hipLaunchKernelGGL((quant_act_conv_kernel<TIn, true, 4, 4, 16>), dim3(tiles, 1, n), dim3(1024), lds5, st, bt);
-            else hipLaunchKernelGGL((quant_act_conv_kernel<TIn, false, 4, 4, 16>), dim3(tiles, 1, n), dim3(1024), lds5, st, bt);
-        }
-        else {
-            // 8 positions per tile, 16 waves: two waves per position (the per-K row sum then adds its two parts: last-bit differences
-            // against the one-wave order; per-M sums are exact integers)
-            if (per_m) hipLaunchKernelGGL((quant_act_conv_kernel<TIn, true, 2, 4, 16>), dim3(tiles, 1, n), dim3(1024), lds5, st, bt);
-            else hipLaunchKernelGGL((quant_act_conv_kernel<TIn, false, 2, 4, 16>), dim3(tiles, 1, n), dim3(1024), lds5, st, bt);
-        }
+#define DGQ_QA_CONV(TH_, TW_, NW_) \
+    DGQ_QA_PER_M(per_m, hipLaunchKernelGGL((quant_act_conv_kernel<TIn, PM, TH_, TW_, NW_>), dim3(tiles, 1, n), dim3(64 * NW_), lds5, st, bt))
+        // 4 x 4: one wave per output position (16 waves) instead of two positions per wave — the gather / quantise phase is a chain of
+        // dependent LDS reads per 1024 codes, and twice the waves hide twice the latency (same lanes, same order per row: bit-identical;
+        // step +0.3-0.5 % same box).  2 x 4, 16 waves: two waves per position (the per-K row sum then adds its two parts: last-bit
+        // differences against the one-wave order; per-M sums are exact integers)
+        if (t.id == 1) DGQ_QA_CONV(4, 8, 8);
+        else if (t.id == 2) DGQ_QA_CONV(4, 4, 16);
+        else DGQ_QA_CONV(2, 4, 16);
 #undef DGQ_QA_CONV
         return;
     }
     if (variant == 3 || variant == 4) {
         size_t lds = 0;
         for (int i = 0; i < n; ++i) {
-            const size_t tab = (((size_t)3 * (bt.p[i].Kp >> 5) + 16) * 4 + 15) & ~(size_t)15;
-            lds = std::max(lds, tab + (variant == 3 ? 4 : 1) * (size_t)bt.p[i].Kp);
+            lds = std::max(lds, (size_t)quant_scatter_table_bytes(bt.p[i].Kp) + (variant == 3 ? 4 : 1) * (size_t)bt.p[i].Kp);
         }
         static std::atomic<bool> attr_set[64];
         dgq_allow_dynamic_lds(attr_set, {{&quant_act_scatter_kernel<TIn, 4, 8>, 152 * 1024},
@@ -789,8 +780,7 @@ static void launch_quant_act(const QuantActBatch& bt, int n, int variant, bool p
     if (variant == 0) {
         const int nw = 4;                                                       // waves (= rows) per block, <= 64 KB of LDS
         dim3 sgrid((p0.M + nw - 1) / nw, ks, n), sblock(64 * nw);
-        if (per_m) hipLaunchKernelGGL((quant_act_staged_kernel<TIn, true>), sgrid, sblock, nw * strip_bytes, st, bt);
-        else hipLaunchKernelGGL((quant_act_staged_kernel<TIn, false>), sgrid, sblock, nw * strip_bytes, st, bt);
+        DGQ_QA_PER_M(per_m, hipLaunchKernelGGL((quant_act_staged_kernel<TIn, PM>), sgrid, sblock, nw * strip_bytes, st, bt));
         return;
     }
     // shared-input form: 2..4 natural-order per-M problems that differ only in tables and outputs (q / k / v of a self-attention)
@@ -813,13 +803,8 @@ static void launch_quant_act(const QuantActBatch& bt, int n, int variant, bool p
         }
     }
     dim3 grid((p0.M + 3) / 4, ks, n), block(256);
-    if (variant == 1) {
-        if (per_m) hipLaunchKernelGGL((quant_act_kernel<TIn, true, true>), grid, block, 0, st, bt);
-        else hipLaunchKernelGGL((quant_act_kernel<TIn, true, false>), grid, block, 0, st, bt);
-    } else {
-        if (per_m) hipLaunchKernelGGL((quant_act_kernel<TIn, false, true>), grid, block, 0, st, bt);
-        else hipLaunchKernelGGL((quant_act_kernel<TIn, false, false>), grid, block, 0, st, bt);
-    }
+    if (variant == 1) DGQ_QA_PER_M(per_m, hipLaunchKernelGGL((quant_act_kernel<TIn, true, PM>), grid, block, 0, st, bt));
+    else DGQ_QA_PER_M(per_m, hipLaunchKernelGGL((quant_act_kernel<TIn, false, PM>), grid, block, 0, st, bt));
 }
 
 extern "C" int dgq_quant_act_parts(int Kp, int ksplits) {
@@ -829,40 +814,32 @@ extern "C" int dgq_quant_act_parts(int Kp, int ksplits) {
 }
 
 static int fill_quant_act(const dgq_quant_act_args_t& a, QuantActParams& p) {
-    DGQ_CHECK_ARG(a.x && a.delta && a.zp && a.codes && a.rowsum, "dgq_quant_act: null pointer");
-    DGQ_CHECK_ARG(a.B > 0 && a.H > 0 && a.W > 0 && a.C > 0 && a.kh > 0 && a.kw > 0 && a.stride > 0 && a.pad >= 0,
-                  "dgq_quant_act: bad geometry");
-    DGQ_CHECK_ARG(a.kh <= 0x7F && a.kw <= 0xFF && a.C <= 0xFFFF, "dgq_quant_act: kernel/channel count out of range");
+    DGQ_CHECK_ARG(a.delta && a.zp && a.codes && a.rowsum, "dgq_quant_act: null pointer");
+    QuantRowInput in;
+    int Ho, Wo;
+    const int rc = dgq_check_quant_input(a, "dgq_quant_act", {1, true, false}, in, Ho, Wo);
+    if (rc != DGQ_OK) return rc;
     DGQ_CHECK_ARG(a.Kp > 0 && a.Kp % DGQ_KTILE == 0, "dgq_quant_act: Kp=%d must be a multiple of %d", a.Kp, DGQ_KTILE);
-    DGQ_CHECK_ARG(a.bits >= 2 && a.bits <= 8, "dgq_quant_act: bits=%d", a.bits);
     DGQ_CHECK_ARG(!a.per_m || a.L >= 1, "dgq_quant_act: per_m needs L >= 1");
     DGQ_CHECK_ARG(a.ksplits >= 1 && a.ksplits <= 64, "dgq_quant_act: ksplits=%d", a.ksplits);
-    DGQ_CHECK_ARG((a.pre_scale == nullptr) == (a.pre_shift == nullptr) && a.pre_act >= 0 && a.pre_act <= 2, "dgq_quant_act: bad prologue");
-    DGQ_CHECK_ARG(a.pre_act != 2 || (a.kh == 1 && a.kw == 1 && !a.pre_scale), "dgq_quant_act: GEGLU prologue is for Linear inputs");
-    DGQ_CHECK_ARG((a.ln_gamma == nullptr) == (a.ln_beta == nullptr), "dgq_quant_act: LayerNorm prologue needs gamma and beta");
-    DGQ_CHECK_ARG(!a.ln_gamma || (a.kh == 1 && a.kw == 1 && !a.pre_scale && a.pre_act == 0 && a.C % 4 == 0 && a.C <= DGQ_LN_MAX_C && a.ln_eps > 0.0f),
-                  "dgq_quant_act: LayerNorm prologue is for Linear inputs (1x1, C %% 4 == 0, C <= 2048, no other prologue)");
     const int K = a.C * a.kh * a.kw;
     if (!a.ksrc) {
         DGQ_CHECK_ARG(a.C % 4 == 0, "dgq_quant_act: natural K order needs C %% 4 == 0 (C=%d)", a.C);
         DGQ_CHECK_ARG(a.Kp >= K, "dgq_quant_act: natural K order needs Kp >= K");
     }
-    const int Ho = (a.H + 2 * a.pad - a.kh) / a.stride + 1, Wo = (a.W + 2 * a.pad - a.kw) / a.stride + 1;
-    DGQ_CHECK_ARG(Ho > 0 && Wo > 0, "dgq_quant_act: empty output");
-    p.x = a.x; p.B = a.B; p.H = a.H; p.W = a.W; p.C = a.C; p.kh = a.kh; p.kw = a.kw; p.stride = a.stride; p.pad = a.pad;
+    p.x = in.x; p.B = a.B; p.H = a.H; p.W = a.W; p.C = in.C; p.kh = a.kh; p.kw = a.kw; p.stride = a.stride; p.pad = a.pad;
     p.Ho = Ho; p.Wo = Wo; p.ksrc = a.ksrc; p.koff = a.ksrc ? a.koff : nullptr; p.klds = a.ksrc ? a.klds : nullptr;
     p.kdst = a.ksrc ? a.kdst : nullptr;
     p.kpat = a.kpat;
     p.Kp = a.Kp; p.K = K; p.delta = a.delta; p.zp = a.zp; p.L = a.per_m ? a.L : 1;
-    p.qmax = (float)((1 << a.bits) - 1);
+    p.qmax = in.levels;
     p.offset = (float)(1 << (a.bits - 1));
     p.codes = a.codes; p.rowsum = a.rowsum; p.M = a.B * Ho * Wo;
     p.kp_per_split = (((a.Kp + a.ksplits - 1) / a.ksplits) + 255) / 256 * 256;
-    p.pre_scale = a.pre_scale; p.pre_shift = a.pre_shift; p.pre_act = a.pre_act;
-    p.ln_gamma = a.ln_gamma; p.ln_beta = a.ln_beta; p.ln_eps = a.ln_eps;
-    p.ldc = a.pre_act == 2 ? 2 * a.C : a.C;
+    p.pre_scale = in.pre_scale; p.pre_shift = in.pre_shift; p.pre_act = in.pre_act;
+    p.ln_gamma = in.ln_gamma; p.ln_beta = in.ln_beta; p.ln_eps = in.ln_eps;
+    p.ldc = in.ldc;
     p.ups = a.ups ? 1 : 0;
-    DGQ_CHECK_ARG(!p.ups || (a.H % 2 == 0 && a.W % 2 == 0 && a.kh * a.kw > 1), "dgq_quant_act: ups needs even H, W and a convolution");
     return DGQ_OK;
 }
 
@@ -888,12 +865,7 @@ extern "C" int dgq_quant_act_batch(int n, const dgq_quant_act_args_t* args, void
     }
     hipStream_t st = (hipStream_t)stream;
     const bool per_m = args[0].per_m != 0;
-    switch (args[0].x_dtype) {
-        case DGQ_F32: launch_quant_act<float>(bt, n, variant, per_m, st); break;
-        case DGQ_F16: launch_quant_act<__half>(bt, n, variant, per_m, st); break;
-        case DGQ_BF16: launch_quant_act<__hip_bfloat16>(bt, n, variant, per_m, st); break;
-        default: dgq_set_error("dgq_quant_act: unknown dtype %d", args[0].x_dtype); return DGQ_EINVAL;
-    }
+    DGQ_QUANT_DTYPE_SWITCH(args[0].x_dtype, "dgq_quant_act", launch_quant_act<TIn>(bt, n, variant, per_m, st))
     return dgq_launch_status("dgq_quant_act");
 }
 

@@ -20,38 +20,31 @@
 #include "quant_prologue.h"
 
 struct BlockQuantProblem {
-    const void* x;
-    int rows, rows_per_image, C, ldc;
-    const float* pre_scale; const float* pre_shift; int pre_act;
-    const float* ln_gamma; const float* ln_beta; float ln_eps;
-    float levels, qmax, offset;
+    QuantRowInput in;
+    float qmax, offset;
     int8_t* codes; float2* table; int ldt; float* rho;
 };
 
 template <typename TIn>
 __global__ __launch_bounds__(256) void quant_block_kernel(BlockQuantProblem p) {
+    const QuantRowInput& in = p.in;
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= p.rows) return;                              // whole wave leaves; no barriers below
-    const TIn* xr = reinterpret_cast<const TIn*>(p.x) + (int64_t)row * p.ldc;
-    const int b = row / p.rows_per_image;
-    const float* pre_sc = p.pre_scale ? p.pre_scale + (int64_t)b * p.C : nullptr;
-    const float* pre_sh = p.pre_shift ? p.pre_shift + (int64_t)b * p.C : nullptr;
-    float ln_mu = 0.0f, ln_rstd = 1.0f;
-    if (p.ln_gamma) row_layernorm_stats<TIn>(xr, p.C, p.ln_eps, lane, ln_mu, ln_rstd);
-    int8_t* crow = p.codes + (int64_t)row * p.C;
+    if (row >= in.rows) return;                             // whole wave leaves; no barriers below
+    const QuantRowSource<TIn> s = quant_row_source<TIn>(in, row, lane);
+    int8_t* crow = p.codes + (int64_t)row * in.C;
     float2* trow = p.table + (int64_t)row * p.ldt;
     float rho = 0.0f;
     // wave-uniform steps of 256 channels = 8 blocks; C % 32 == 0, so the 8 lanes of a block are all inside the row or all past it (a
     // block past the end computes on a clamped address and stores nothing)
-    for (int base = 0; base < p.C; base += 256) {
+    for (int base = 0; base < in.C; base += 256) {
         const int c0 = base + lane * 4;
-        const bool in = c0 < p.C;
-        const int c = min(c0, p.C - 4);
+        const bool inside = c0 < in.C;
+        const int c = min(c0, in.C - 4);
         float v[4], g[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        load4<TIn>(xr + c, v);
-        if (p.pre_act == 2) load4<TIn>(xr + p.C + c, g);
-        dgq_prologue4(v, c, pre_sc, pre_sh, p.ln_gamma, p.ln_beta, ln_mu, ln_rstd, p.pre_act, g);
+        load4<TIn>(s.xr + c, v);
+        if (in.pre_act == 2) load4<TIn>(s.xr + in.C + c, g);
+        dgq_prologue4(v, c, s.pre_sc, s.pre_sh, in.ln_gamma, in.ln_beta, s.ln_mu, s.ln_rstd, in.pre_act, g);
         float mn = fminf(0.0f, fminf(fminf(v[0], v[1]), fminf(v[2], v[3])));       // MINMAX includes 0 in the range
         float mx = fmaxf(0.0f, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
 #pragma unroll
@@ -60,7 +53,7 @@ __global__ __launch_bounds__(256) void quant_block_kernel(BlockQuantProblem p) {
             mx = fmaxf(mx, __shfl_xor(mx, o, 64));
         }
         float d, z;
-        minmax_params(mn, mx, p.levels, d, z);
+        minmax_params(mn, mx, in.levels, d, z);
         float q[4];
         dgq_affine_code4_fast(v, d, dgq_rcp(d), z, p.qmax, q);
         const float biased[4] = {q[0] - p.offset + 128.0f, q[1] - p.offset + 128.0f, q[2] - p.offset + 128.0f, q[3] - p.offset + 128.0f};
@@ -69,7 +62,7 @@ __global__ __launch_bounds__(256) void quant_block_kernel(BlockQuantProblem p) {
         float rs = fs - 512.0f;                              // Σ s of the lane's four codes, then of the block (exact integers)
 #pragma unroll
         for (int o = 1; o < 8; o <<= 1) rs += __shfl_xor(rs, o, 64);
-        if (in) {
+        if (inside) {
             *reinterpret_cast<uint32_t*>(crow + c) = w;
             if ((lane & 7) == 0) trow[c >> 5] = make_float2(d, d * (p.offset - z));
         }
@@ -77,10 +70,10 @@ __global__ __launch_bounds__(256) void quant_block_kernel(BlockQuantProblem p) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {                        // ascending block order, the same chain in every lane
             const float t = __shfl(term, 8 * j, 64);
-            if (base + 32 * j < p.C) rho += t;
+            if (base + 32 * j < in.C) rho += t;
         }
     }
-    for (int cb = (p.C >> 5) + lane; cb < p.ldt; cb += 64) trow[cb] = make_float2(0.0f, 0.0f);
+    for (int cb = (in.C >> 5) + lane; cb < p.ldt; cb += 64) trow[cb] = make_float2(0.0f, 0.0f);
     if (lane == 0) p.rho[row] = rho;
 }
 
@@ -88,38 +81,20 @@ extern "C" int dgq_quant_act_block(const dgq_quant_act_args_t* in, const dgq_act
     DGQ_CHECK_ARG(in && out, "dgq_quant_act_block: null pointer");
     const dgq_quant_act_args_t& a = *in;
     const dgq_act_block_out_t& o = *out;
-    DGQ_CHECK_ARG(a.x && o.codes && o.table && o.rho, "dgq_quant_act_block: null pointer");
-    DGQ_CHECK_ARG(((uintptr_t)a.x & 15) == 0 && ((uintptr_t)o.codes & 15) == 0 && ((uintptr_t)o.table & 7) == 0,
-                  "dgq_quant_act_block: x / codes must be 16-byte aligned, the table 8-byte aligned");
-    DGQ_CHECK_ARG(a.B > 0 && a.H > 0 && a.W > 0 && a.C > 0, "dgq_quant_act_block: bad geometry");
-    DGQ_CHECK_ARG(a.C % DGQ_KCHUNK == 0, "dgq_quant_act_block: C=%d must be a multiple of %d", a.C, DGQ_KCHUNK);
-    DGQ_CHECK_ARG(o.ldt >= a.C / DGQ_KCHUNK, "dgq_quant_act_block: table pitch %d < %d blocks", o.ldt, a.C / DGQ_KCHUNK);
-    DGQ_CHECK_ARG(a.bits >= 2 && a.bits <= 8, "dgq_quant_act_block: bits=%d", a.bits);
-    DGQ_CHECK_ARG((a.pre_scale == nullptr) == (a.pre_shift == nullptr) && a.pre_act >= 0 && a.pre_act <= 2, "dgq_quant_act_block: bad prologue");
-    const bool one = a.kh == 1 && a.kw == 1;
-    DGQ_CHECK_ARG(a.pre_act != 2 || (one && !a.pre_scale), "dgq_quant_act_block: GEGLU prologue is for Linear inputs");
-    DGQ_CHECK_ARG((a.ln_gamma == nullptr) == (a.ln_beta == nullptr), "dgq_quant_act_block: LayerNorm prologue needs gamma and beta");
-    DGQ_CHECK_ARG(!a.ln_gamma || (one && !a.pre_scale && a.pre_act == 0 && a.C <= DGQ_LN_MAX_C && a.ln_eps > 0.0f),
-                  "dgq_quant_act_block: LayerNorm prologue is for Linear inputs (1x1, C <= 2048, no other prologue)");
-    const int ups = a.ups ? 1 : 0;
-    DGQ_CHECK_ARG(!ups || (a.H % 2 == 0 && a.W % 2 == 0), "dgq_quant_act_block: ups needs even H, W");
-    const int Hs = a.H >> ups, Ws = a.W >> ups;
-    const int64_t rows = (int64_t)a.B * Hs * Ws;
-    DGQ_CHECK_ARG(rows < (1LL << 30) && rows * a.C < (1LL << 40), "dgq_quant_act_block: too many rows");
+    DGQ_CHECK_ARG(o.codes && o.table && o.rho, "dgq_quant_act_block: null pointer");
+    DGQ_CHECK_ARG(((uintptr_t)o.codes & 15) == 0 && ((uintptr_t)o.table & 7) == 0,
+                  "dgq_quant_act_block: codes must be 16-byte aligned, the table 8-byte aligned");
     BlockQuantProblem p;
-    p.x = a.x; p.rows = (int)rows; p.rows_per_image = Hs * Ws; p.C = a.C; p.ldc = a.pre_act == 2 ? 2 * a.C : a.C;
-    p.pre_scale = a.pre_scale; p.pre_shift = a.pre_shift; p.pre_act = a.pre_act;
-    p.ln_gamma = a.ln_gamma; p.ln_beta = a.ln_beta; p.ln_eps = a.ln_eps;
-    p.levels = (float)((1 << a.bits) - 1); p.qmax = p.levels; p.offset = (float)(1 << (a.bits - 1));
+    int Ho, Wo;
+    const int rc = dgq_check_quant_input(a, "dgq_quant_act_block", {DGQ_KCHUNK, false, true}, p.in, Ho, Wo);
+    if (rc != DGQ_OK) return rc;
+    DGQ_CHECK_ARG(o.ldt >= a.C / DGQ_KCHUNK, "dgq_quant_act_block: table pitch %d < %d blocks", o.ldt, a.C / DGQ_KCHUNK);
+    DGQ_CHECK_ARG((int64_t)p.in.rows * a.C < (1LL << 40), "dgq_quant_act_block: too many rows");
+    p.qmax = p.in.levels; p.offset = (float)(1 << (a.bits - 1));
     p.codes = o.codes; p.table = reinterpret_cast<float2*>(o.table); p.ldt = o.ldt; p.rho = o.rho;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((p.rows + 3) / 4), block(256);
-    switch (a.x_dtype) {
-        case DGQ_F32: hipLaunchKernelGGL((quant_block_kernel<float>), grid, block, 0, st, p); break;
-        case DGQ_F16: hipLaunchKernelGGL((quant_block_kernel<__half>), grid, block, 0, st, p); break;
-        case DGQ_BF16: hipLaunchKernelGGL((quant_block_kernel<__hip_bfloat16>), grid, block, 0, st, p); break;
-        default: dgq_set_error("dgq_quant_act_block: unknown dtype %d", a.x_dtype); return DGQ_EINVAL;
-    }
+    const dim3 grid((p.in.rows + 3) / 4), block(256);
+    DGQ_QUANT_DTYPE_SWITCH(a.x_dtype, "dgq_quant_act_block", hipLaunchKernelGGL((quant_block_kernel<TIn>), grid, block, 0, st, p))
     return dgq_launch_status("dgq_quant_act_block");
 }
 
@@ -146,11 +121,7 @@ extern "C" int dgq_dequant_act_block(const int8_t* codes, const float* table, in
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((rows * C / 4 + 255) / 256)), block(256);
     const float2* tb = reinterpret_cast<const float2*>(table);
-    switch (y_dtype) {
-        case DGQ_F32: hipLaunchKernelGGL((dequant_block_kernel<float>), grid, block, 0, st, codes, tb, ldt, rows, C, reinterpret_cast<float*>(y)); break;
-        case DGQ_F16: hipLaunchKernelGGL((dequant_block_kernel<__half>), grid, block, 0, st, codes, tb, ldt, rows, C, reinterpret_cast<__half*>(y)); break;
-        case DGQ_BF16: hipLaunchKernelGGL((dequant_block_kernel<__hip_bfloat16>), grid, block, 0, st, codes, tb, ldt, rows, C, reinterpret_cast<__hip_bfloat16*>(y)); break;
-        default: dgq_set_error("dgq_dequant_act_block: unknown dtype %d", y_dtype); return DGQ_EINVAL;
-    }
+    DGQ_QUANT_DTYPE_SWITCH(y_dtype, "dgq_dequant_act_block",
+                           hipLaunchKernelGGL((dequant_block_kernel<TIn>), grid, block, 0, st, codes, tb, ldt, rows, C, reinterpret_cast<TIn*>(y)))
     return dgq_launch_status("dgq_dequant_act_block");
 }
