@@ -51,11 +51,16 @@ def parse_args(argv=None):
     p.add_argument("--aq_real_time_block", type=int, default=0,
                    help="with --aq_real_time: 32 = one pair per row and block of 32 consecutive channels (dgq_quant_act_block + "
                         "dgq_gemm_blockq); 0 = one pair per row")
+    p.add_argument("--wq_mfma16", action="store_true",
+                   help="weight-only state (no --use_aq): run the layers on the bf16 / f16 matrix cores (dgq_conv2d_wq_mfma16) — faster, "
+                        "not bit-identical to the default exact route")
     return p.parse_args(argv)
 
 
 def main(argv=None):
     opt = parse_args(argv)
+    if opt.wq_mfma16 and opt.use_aq:
+        raise SystemExit("--wq_mfma16 selects a route of the weight-only state: it cannot be combined with --use_aq")
     if opt.aq_real_time_block and not (opt.use_aq and opt.aq_real_time):       # (a bad command line exits before anything is built)
         raise SystemExit("--aq_real_time_block is a granularity of the real-time mode: it needs --use_aq --aq_real_time")
     if opt.aq_real_time_block not in (0, 32):
@@ -111,6 +116,8 @@ def main(argv=None):
     qnn = qnn.half() if opt.fp16 else qnn.float()
     qnn = qnn.to(dev)
     qnn.disable_out_quantization()
+    if opt.wq_mfma16:
+        qnn.set_weight_only_mfma16(True)
     if opt.graphs:
         qnn.enable_graphs(True)
     dt = torch.float16 if opt.fp16 else torch.float32

@@ -160,6 +160,24 @@ class PackedWeight:
         self._natural_frag = None
         self._vn = None
         self._vc = None
+        self._mfma16 = None
+
+    def mfma16_eligible(self):
+        """True when dgq_conv2d_wq_mfma16 may take this weight: the zero points are integers and every q − z fits the bound (15 for
+        W4, 255 for W8), so that q − z is exact in bf16 and f16 — MINMAX and AdaRound checkpoints (their z is a rounded value inside
+        the code range).  Computed once per packed weight."""
+        if self._mfma16 is None:
+            self._mfma16 = self.check_mfma16(self.codes, self.zp_true, self.bits)
+        return self._mfma16
+
+    @staticmethod
+    def check_mfma16(codes, zp, bits):
+        """the rule of mfma16_eligible on codes [N][K] (u8) and zero points [N] (any device)"""
+        z = zp.reshape(-1).float()
+        lim = 15 if bits == 4 else 255
+        if not (bool(torch.isfinite(z).all()) and bool((z == z.round()).all())):
+            return False
+        return bool(((codes.float() - z[:, None]).abs() <= lim).all())
 
     def natural_frag(self):
         """the natural-order weights fragment-major (dgq_pack_w4 layout 2), W4 only; None otherwise"""
@@ -1207,6 +1225,24 @@ def conv2d_wq(x: torch.Tensor, pw: PackedWeight, kh, kw, stride, pad, upsample=F
     M = B * ((H + 2 * pad - kh) // stride + 1) * ((W + 2 * pad - kw) // stride + 1)
     y = torch.empty((M, N), dtype=x.dtype, device=x.device)
     _lib_call("dgq_conv2d_wq", _lib.ptr(xs), _lib.DTYPE_CODE[x.dtype], *geom, int(upsample),
+              _lib.ptr(w_img), pw.bits, Kp, _lib.ptr(pw.alpha), _lib.ptr(pw.zp_true), _lib.ptr(pw.bias), N, int(geglu_rows),
+              _lib.ptr(y), _lib.DTYPE_CODE[y.dtype], N, _lib.stream())
+    return result(y)
+
+
+def conv2d_wq_mfma16(x: torch.Tensor, pw: PackedWeight, kh, kw, stride, pad, upsample=False, geglu_rows=False):
+    """Weight-only state on the bf16 / f16 matrix cores (dgq_conv2d_wq_mfma16), beside conv2d_wq: the same operands, arguments and
+    returned views, NOT the same bits — y = b + δ·Σ_k x̃·(q − z) with the integer q − z as the 16-bit operand, fp32 accumulation in
+    the kernel's own order and δ in the epilogue.  bf16 / f16 x enter as they are; fp32 x as two bf16 terms (|x − x̃| <= 2^-16·|x|).
+    pw.mfma16_eligible() must hold (the caller's check: QuantLayer routes an ineligible weight to conv2d_wq)."""
+    assert pw.mfma16_eligible(), "dgq conv2d_wq_mfma16: q − z is not an integer within the operand's exact range"
+    w_img, Kp = pw.natural()
+    N = pw.N
+    xs, geom, result = _weight_only_operand(x, pw.K, kh, kw, stride, pad, upsample, "conv2d_wq_mfma16")
+    B, H, W = geom[:3]
+    M = B * ((H + 2 * pad - kh) // stride + 1) * ((W + 2 * pad - kw) // stride + 1)
+    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    _lib_call("dgq_conv2d_wq_mfma16", _lib.ptr(xs), _lib.DTYPE_CODE[x.dtype], *geom, int(upsample),
               _lib.ptr(w_img), pw.bits, Kp, _lib.ptr(pw.alpha), _lib.ptr(pw.zp_true), _lib.ptr(pw.bias), N, int(geglu_rows),
               _lib.ptr(y), _lib.DTYPE_CODE[y.dtype], N, _lib.stream())
     return result(y)

@@ -469,6 +469,10 @@ class QuantLayer(nn.Module):
     """Drop-in for the reference's QuantLayer (quant_layer.py:577-702) around nn.Linear / nn.Conv2d."""
 
     QMAP = {nn.Conv2d: F.conv2d, nn.Linear: F.linear}
+    #: opt-in, read at call time: where forward / forward_upsampled would run dgq_conv2d_wq, run dgq_conv2d_wq_mfma16 instead (the
+    #: 16-bit matrix cores: not bit-identical to the exact route, DESIGN.md §8) — see takes_mfma16.  QuantModel.set_weight_only_mfma16
+    #: sets it on every layer.
+    weight_only_mfma16 = False
 
     def __init__(self, layer: Union[nn.Conv2d, nn.Linear], wq_params: dict = {}, aq_params: dict = {},
                  disable_aq: bool = False, aq_mode: List[int] = [QMODE.QDIFF.value], quant_emb: bool = False) -> None:
@@ -671,7 +675,7 @@ class QuantLayer(nn.Module):
                 # inference in the weight-only state: exact-fp32 MFMA kernel of this library, not F.linear / F.conv2d of the
                 # vendor libraries — from the packed codes (dgq_conv2d_wq), or on the dequantised fp32 weight (dgq_conv2d_f32w)
                 if self.on_packed_weight_only_path(x):
-                    return ops.conv2d_wq(x, self.packed_weight(), *self._conv_geom(), geglu_rows=self.geglu_rows)
+                    return self._weight_only_op()(x, self.packed_weight(), *self._conv_geom(), geglu_rows=self.geglu_rows)
                 if self._weight_only_hip(x):
                     return ops.conv2d_f32w(x, *self.dequantized_weight_natural(), *self._conv_geom())
                 w = self.dequantized_weight(x.dtype)
@@ -729,7 +733,7 @@ class QuantLayer(nn.Module):
         (ops.conv2d_wq(upsample=True)), under the same conditions."""
         if (LAYER_TAP is None and self.is_conv and self.on_packed_weight_only_path(x) and not self.aqtizer.calibrating()
                 and not self._forward_hooks and not self._forward_pre_hooks):
-            return ops.conv2d_wq(x, self.packed_weight(), *self._conv_geom(), upsample=True)
+            return self._weight_only_op()(x, self.packed_weight(), *self._conv_geom(), upsample=True)
         if (LAYER_TAP is None and self.is_conv and self.on_integer_path(x) and x.dtype in ops.FLOAT_DTYPES and not self.aqtizer.calibrating()
                 and not self._forward_hooks and not self._forward_pre_hooks and self.taps > 1):
             out, out2 = self._take_redirect(x, 2) if final else (None, None)
@@ -740,6 +744,16 @@ class QuantLayer(nn.Module):
         """True when forward(x) would run dgq_conv2d_wq (weight-only state from the packed codes, GPU, outside autograd)."""
         return (WEIGHT_ONLY_PACKED and self.use_wq and not (self.use_aq and not self.disable_aq) and x.is_cuda
                 and not getattr(self.wqtizer, "soft_tgt", False) and self.w.shape[0] > 8 and self._weight_only_hip(x))
+
+    def takes_mfma16(self) -> bool:
+        """True when a call on the packed weight-only path runs dgq_conv2d_wq_mfma16 instead of dgq_conv2d_wq: the switch is set and
+        the weight is eligible (PackedWeight.mfma16_eligible: integral zero points, q − z within the operand's exact range; a weight
+        that is not stays on the exact route).  There is no rule on the shape: every row of profiles/r13_weight_only_mfma16.txt is
+        faster on the new kernel, the M = batch time-embedding layers (time_embedding, time_emb_proj) included, so they take it too."""
+        return self.weight_only_mfma16 and self.packed_weight().mfma16_eligible()
+
+    def _weight_only_op(self):
+        return ops.conv2d_wq_mfma16 if self.takes_mfma16() else ops.conv2d_wq
 
     def _weight_only_hip(self, x: torch.Tensor) -> bool:
         """what the weight-only state asks of x and of the layer before it leaves F.conv2d / F.linear for this library's kernels"""

@@ -103,6 +103,15 @@ class QuantModel(nn.Module):
             if isinstance(m, (BaseQuantBlock, QuantLayer)):
                 m.set_quant_state(use_wq=use_wq, use_aq=use_aq)
 
+    def set_weight_only_mfma16(self, flag: bool = True) -> None:
+        """Opt in to (or out of) the 16-bit matrix-core route of the weight-only state (QuantLayer.weight_only_mfma16) on every
+        layer.  Off by default: the route is faster and not bit-identical to the exact one.  It means something in
+        the weight-only state only; the other states never read it."""
+        self._drop_graphs()
+        for m in self.model.modules():
+            if isinstance(m, QuantLayer):
+                m.weight_only_mfma16 = bool(flag)
+
     def disable_out_quantization(self) -> None:
         """conv_in / conv_out stay floating point (quant_model.py:118-124)."""
         self._drop_graphs()

@@ -45,7 +45,8 @@ extern "C" {
  *   123  dgq_conv2d_wq (the weight-only state from the packed W4 / W8 codes); later, without a new revision because no existing
  *        entry or struct changed (a binding written against 123 keeps working): the real-time per-row activation quantiser tables,
  *        dgq_act_row_params / dgq_act_row_params_batch with their dgq_act_rowparams_out_t; the real-time block mode,
- *        dgq_quant_act_block / dgq_dequant_act_block / dgq_gemm_blockq with dgq_act_block_out_t and dgq_gemm_block_t */
+ *        dgq_quant_act_block / dgq_dequant_act_block / dgq_gemm_blockq with dgq_act_block_out_t and dgq_gemm_block_t; dgq_conv2d_wq_mfma16 (the weight-only
+ *        state on the 16-bit matrix cores) */
 #define DGQ_ABI_VERSION 123
 int dgq_version(void);
 const char* dgq_last_error(void);
@@ -235,6 +236,17 @@ int dgq_conv2d_f32w(const void* x, int x_dtype, int B, int H, int W, int C, int 
 int dgq_conv2d_wq(const void* x, int x_dtype, int B, int H, int W, int C, int kh, int kw, int stride, int pad, int upsample,
                   const uint8_t* w_packed, int w_bits, int Kp, const float* delta, const float* zp, const float* bias, int N,
                   int geglu_rows, void* y, int y_dtype, int ldy, void* stream);
+
+/* dgq_conv2d_wq_mfma16: the same layer, arguments and refusals on the 16-bit matrix cores — NOT bit-identical to dgq_conv2d_wq:
+ *   y[m,n] = round_to_y( bias[n] + delta[n]·Σ_k x̃[m,k]·(q[n,k] − zp[n]) ),  k in (tap, c) order, fp32 accumulation, one K loop per
+ * workgroup (no K split, no atomics: the order of summation is fixed by the shape).  q − zp[n] is converted once, as it is staged, to
+ * the operand type: bf16 for bf16 and fp32 x, f16 for f16 x.  The caller guarantees that it is an integer of magnitude <= 15 (W4) /
+ * 255 (W8) — exact in both types (PackedWeight.mfma16_eligible); another value is rounded to the operand type.  bf16 / f16 x: x̃ = x,
+ * the products are exact in fp32.  fp32 x: x̃ = hi + lo with hi = bf16_rn(x), lo = bf16_rn(x − hi), |x − x̃| <= 2^-16·|x|; two MFMAs
+ * per K step into one accumulator, first lo, then hi. */
+int dgq_conv2d_wq_mfma16(const void* x, int x_dtype, int B, int H, int W, int C, int kh, int kw, int stride, int pad, int upsample,
+                         const uint8_t* w_packed, int w_bits, int Kp, const float* delta, const float* zp, const float* bias, int N,
+                         int geglu_rows, void* y, int y_dtype, int ldy, void* stream);
 
 /* ---- the hot kernel: W4A8 / W8A8 MFMA GEMM with fused dequantisation ------------------------------
  * Replaces F.linear / `w.view(N,-1) @ unfolded` / F.conv2d on fake-quantised operands
