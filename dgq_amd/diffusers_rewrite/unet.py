@@ -209,6 +209,11 @@ class ResnetBlock2D(nn.Module):
 
 
 class Attention(nn.Module):
+    #: opt-in, read at call time by quant_block.quant_attention_forward: un-quantised attention on fp16 / bf16 tensors runs
+    #: dgq_attention_mfma16 (one launch on the 16-bit matrix cores) instead of the materialised torch formulation.
+    #: QuantModel.set_attention_mfma16 sets it on every attention; the quantised modes, the fp32 state and the CPU never read it.
+    attention_mfma16 = False
+
     def __init__(self, inner_dim, cross_attention_dim=None, num_heads=None, head_dim=None):
         super().__init__()
         if num_heads is None:

@@ -54,6 +54,9 @@ def parse_args(argv=None):
     p.add_argument("--wq_mfma16", action="store_true",
                    help="weight-only state (no --use_aq): run the layers on the bf16 / f16 matrix cores (dgq_conv2d_wq_mfma16) — faster, "
                         "not bit-identical to the default exact route")
+    p.add_argument("--attn_mfma16", action="store_true",
+                   help="with --fp16 and no --use_aq: run the un-quantised attentions on the f16 matrix cores in one launch "
+                        "(dgq_attention_mfma16) instead of matmul / softmax / matmul — faster, differs by rounding")
     return p.parse_args(argv)
 
 
@@ -61,6 +64,10 @@ def main(argv=None):
     opt = parse_args(argv)
     if opt.wq_mfma16 and opt.use_aq:
         raise SystemExit("--wq_mfma16 selects a route of the weight-only state: it cannot be combined with --use_aq")
+    if opt.attn_mfma16 and opt.use_aq:
+        raise SystemExit("--attn_mfma16 selects a route of the un-quantised attention: it cannot be combined with --use_aq")
+    if opt.attn_mfma16 and not opt.fp16:
+        raise SystemExit("--attn_mfma16 serves 16-bit tensors: it needs --fp16 (the fp32 state keeps its exact attention kernel)")
     if opt.aq_real_time_block and not (opt.use_aq and opt.aq_real_time):       # (a bad command line exits before anything is built)
         raise SystemExit("--aq_real_time_block is a granularity of the real-time mode: it needs --use_aq --aq_real_time")
     if opt.aq_real_time_block not in (0, 32):
@@ -118,6 +125,8 @@ def main(argv=None):
     qnn.disable_out_quantization()
     if opt.wq_mfma16:
         qnn.set_weight_only_mfma16(True)
+    if opt.attn_mfma16:
+        qnn.set_attention_mfma16(True)
     if opt.graphs:
         qnn.enable_graphs(True)
     dt = torch.float16 if opt.fp16 else torch.float32

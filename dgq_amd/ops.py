@@ -1427,6 +1427,25 @@ def attention(q, k, v, H, D, scale, mode, skip, delta, bits, fq=None):
 attention_f32 = attention
 
 
+def attention_mfma16(q, k, v, H, D, scale):
+    """Un-quantised attention of the 16-bit states on the bf16 / f16 matrix cores (dgq_attention_mfma16), beside ``attention``: q [B,T,H*D],
+    k/v [B,S,H*D] contiguous fp16 / bf16 of one dtype -> o [B,T,H*D].  One launch, no workspace; fp32 scores and accumulation, the
+    probabilities never leave the registers.  Opt-in through the attention modules' ``attention_mfma16`` flag."""
+    assert q.dtype in (torch.float16, torch.bfloat16) and k.dtype == q.dtype and v.dtype == q.dtype
+    assert q.is_contiguous() and k.is_contiguous() and v.is_contiguous()
+    B, T, _ = q.shape
+    S = k.shape[1]
+    o = torch.empty_like(q)
+
+    def issue():
+        _lib_call("dgq_attention_mfma16", _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), _lib.DTYPE_CODE[q.dtype], B, H, T, S, D,
+                  _c.c_float(scale), _lib.stream())
+    issue()
+    if ATTN_LAUNCH_HOOK is not None:                   # the accounting of ``attention``
+        ATTN_LAUNCH_HOOK(issue, 4.0 * T * S * D * B * H, (2 * B * T + 2 * B * S) * H * D * q.element_size())
+    return o
+
+
 def attention_sync_timeouts():
     """Workgroups of single-launch attention calls (csrc/attn_one.hip) that ever gave up the wait for the real-time δ exchange
     in this process; synchronises.  0 unless a grid was not resident as a whole."""

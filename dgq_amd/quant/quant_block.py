@@ -418,6 +418,12 @@ def quant_attention_forward(attn, hidden_states, encoder_hidden_states=None, res
         o = ops.attention(q.contiguous(), k.contiguous(), v.contiguous(), H, D, float(attn.scale), mode, skip,
                               delta, bits, fq)
         return _attn_out(attn, o, residual)
+    if (not use_aq and getattr(attn, "attention_mfma16", False) and q.is_cuda and q.dtype in (torch.float16, torch.bfloat16)
+            and q.dtype == k.dtype == v.dtype and D in ops.ATTN_HEAD_DIMS and not needs_grad):
+        # opt-in (QuantModel.set_attention_mfma16): the un-quantised attention of the 16-bit states in one launch on the bf16 / f16
+        # matrix cores instead of matmul -> softmax -> matmul below (fp32 scores, probabilities never written out: DESIGN.md §8)
+        o = ops.attention_mfma16(q.contiguous(), k.contiguous(), v.contiguous(), H, D, float(attn.scale))
+        return _attn_out(attn, o, residual)
     qh = q.view(b, t, H, D).transpose(1, 2)
     kh = k.view(b, s, H, D).transpose(1, 2)
     vh = v.view(b, s, H, D).transpose(1, 2)

@@ -112,6 +112,17 @@ class QuantModel(nn.Module):
             if isinstance(m, QuantLayer):
                 m.weight_only_mfma16 = bool(flag)
 
+    def set_attention_mfma16(self, flag: bool = True) -> None:
+        """Opt in to (or out of) dgq_attention_mfma16 on every attention the quant blocks drive (their ``attention_mfma16`` flag): with
+        activation quantisation off, attention on fp16 / bf16 tensors runs in one launch on the 16-bit matrix cores instead of the
+        materialised torch formulation.  Off by default: the result differs from that formulation by rounding.  The
+        quantised modes, the fp32 state and the CPU never read the flag."""
+        self._drop_graphs()
+        for m in self.model.modules():
+            if isinstance(m, QuantBasicTransformerBlock):
+                for attn in (m.attn1, m.attn2):
+                    attn.attention_mfma16 = bool(flag)
+
     def disable_out_quantization(self) -> None:
         """conv_in / conv_out stay floating point (quant_model.py:118-124)."""
         self._drop_graphs()

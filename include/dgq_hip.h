@@ -46,7 +46,7 @@ extern "C" {
  *        entry or struct changed (a binding written against 123 keeps working): the real-time per-row activation quantiser tables,
  *        dgq_act_row_params / dgq_act_row_params_batch with their dgq_act_rowparams_out_t; the real-time block mode,
  *        dgq_quant_act_block / dgq_dequant_act_block / dgq_gemm_blockq with dgq_act_block_out_t and dgq_gemm_block_t; dgq_conv2d_wq_mfma16 (the weight-only
- *        state on the 16-bit matrix cores) */
+ *        state on the 16-bit matrix cores); dgq_attention_mfma16 (un-quantised attention of the 16-bit states on the same cores) */
 #define DGQ_ABI_VERSION 123
 int dgq_version(void);
 const char* dgq_last_error(void);
@@ -462,6 +462,18 @@ size_t dgq_attention_workspace_bytes(int B, int H, int T, int S, int D);
  * gave up that poll in this process (device counter, read with a synchronous copy; 0 unless a grid was not resident — then the
  * affected call's output is invalid); < 0 on a runtime error.  DGQ_ATTN_ONE=0 in the environment keeps every call on three launches. */
 int dgq_attention_sync_timeouts(void);
+
+/* dgq_attention_mfma16: o = softmax((q·kᵀ)·scale)·v with NO quantiser (mode 0 of dgq_attention) on fp16 / bf16 tensors, on the bf16 / f16
+ * matrix cores, in ONE launch with no workspace (csrc/attn_mfma16.hip).  Layout of dgq_attention: q [B][T][H·D], k / v [B][S][H·D],
+ * o [B][T][H·D], all of `dtype` and 16-byte aligned.  Per (batch, head, query): s_j = fp32(Σ_d q_d·k_{j,d})·scale (the 16-bit products are
+ * exact in fp32, fp32 accumulation); online softmax over key tiles in fp32 (running maximum m, p_j = exp(s_j − m), l and the
+ * accumulator rescaled when m moves); p_j is rounded to `dtype` (nearest even) for the P·V product only — l sums the unrounded p_j;
+ * o = round_dtype(acc / l).  Per element |o − o64| <= (2u + 2E + 2^-16)·Σ_j p_j|v_j| + u·|o64|, u = 2^-9 (bf16) / 2^-11 (f16),
+ * E = max_j D·2^-24·scale·Σ_d |q_d·k_{j,d}|.  dtype DGQ_F16 or DGQ_BF16; DGQ_F32 returns DGQ_EUNSUPPORTED (the fp32
+ * state keeps dgq_attention's exact kernel).  D ∈ {8,16,40,64,80,160} (zero padded to the MFMA depth inside the kernel), any
+ * B, H, T, S >= 1 with B·H <= 65535.  Launches on `stream`, allocates nothing, does not synchronise. */
+int dgq_attention_mfma16(const void* q, const void* k, const void* v, void* o, int dtype, int B, int H, int T, int S, int D,
+                         float scale, void* stream);
 
 /* ---- batched small-M Linear ------------------------------------------------------------------------
  * dgq_linear_smallm_batch: y_l = W_l·aqtizer_l(act(x)) + b_l for up to 24 quantized Linear layers that share one input
