@@ -38,6 +38,7 @@ SIGNATURES = {
     "dgq_conv2d_wq": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp],
     "dgq_conv2d_wq_mfma16": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp],
     "dgq_attention_mfma16": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
+    "dgq_attention_mfma16_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],
     "dgq_attention_fuses_fakequant": [_i, _i],
     "dgq_attention_workspace_bytes": [_i, _i, _i, _i, _i],
     "dgq_attention_sync_timeouts": [],

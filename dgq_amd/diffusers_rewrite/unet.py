@@ -213,6 +213,10 @@ class Attention(nn.Module):
     #: dgq_attention_mfma16 (one launch on the 16-bit matrix cores) instead of the materialised torch formulation.
     #: QuantModel.set_attention_mfma16 sets it on every attention; the quantised modes, the fp32 state and the CPU never read it.
     attention_mfma16 = False
+    #: opt-in, a switch of its own: with activation quantisation off, attention on fp32 CUDA tensors runs through dgq_attention_mfma16_f32
+    #: (one launch on the bf16 matrix cores, two-term bf16 splits) instead of dgq_attention mode 0 (the exact fp32 MFMA).
+    #: QuantModel.set_attention_mfma16_fp32 sets it on every attention; the quantised modes, the 16-bit states and the CPU never read it.
+    attention_mfma16_fp32 = False
 
     def __init__(self, inner_dim, cross_attention_dim=None, num_heads=None, head_dim=None):
         super().__init__()

@@ -57,6 +57,9 @@ def parse_args(argv=None):
     p.add_argument("--attn_mfma16", action="store_true",
                    help="with --fp16 and no --use_aq: run the un-quantised attentions on the f16 matrix cores in one launch "
                         "(dgq_attention_mfma16) instead of matmul / softmax / matmul — faster, differs by rounding")
+    p.add_argument("--attn_mfma16_fp32", action="store_true",
+                   help="fp32 state (no --fp16, no --use_aq): run the un-quantised attentions on the bf16 matrix cores in one launch "
+                        "(dgq_attention_mfma16_f32, two-term bf16 splits) instead of the exact fp32 kernel — faster, differs by rounding")
     return p.parse_args(argv)
 
 
@@ -67,7 +70,12 @@ def main(argv=None):
     if opt.attn_mfma16 and opt.use_aq:
         raise SystemExit("--attn_mfma16 selects a route of the un-quantised attention: it cannot be combined with --use_aq")
     if opt.attn_mfma16 and not opt.fp16:
-        raise SystemExit("--attn_mfma16 serves 16-bit tensors: it needs --fp16 (the fp32 state keeps its exact attention kernel)")
+        raise SystemExit("--attn_mfma16 serves 16-bit tensors: it needs --fp16 (the fp32 state keeps its exact attention kernel; "
+                         "--attn_mfma16_fp32 is its switch)")
+    if opt.attn_mfma16_fp32 and opt.use_aq:
+        raise SystemExit("--attn_mfma16_fp32 selects a route of the un-quantised attention: it cannot be combined with --use_aq")
+    if opt.attn_mfma16_fp32 and opt.fp16:
+        raise SystemExit("--attn_mfma16_fp32 serves the fp32 state: it cannot be combined with --fp16 (--attn_mfma16 is the 16-bit switch)")
     if opt.aq_real_time_block and not (opt.use_aq and opt.aq_real_time):       # (a bad command line exits before anything is built)
         raise SystemExit("--aq_real_time_block is a granularity of the real-time mode: it needs --use_aq --aq_real_time")
     if opt.aq_real_time_block not in (0, 32):
@@ -127,6 +135,8 @@ def main(argv=None):
         qnn.set_weight_only_mfma16(True)
     if opt.attn_mfma16:
         qnn.set_attention_mfma16(True)
+    if opt.attn_mfma16_fp32:
+        qnn.set_attention_mfma16_fp32(True)
     if opt.graphs:
         qnn.enable_graphs(True)
     dt = torch.float16 if opt.fp16 else torch.float32

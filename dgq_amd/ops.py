@@ -1446,6 +1446,25 @@ def attention_mfma16(q, k, v, H, D, scale):
     return o
 
 
+def attention_mfma16_f32(q, k, v, H, D, scale):
+    """Un-quantised attention of the fp32 state on the bf16 matrix cores (dgq_attention_mfma16_f32), beside ``attention`` mode 0: q [B,T,H*D],
+    k/v [B,S,H*D] contiguous fp32 -> fp32 o [B,T,H*D].  One launch, no workspace; q, k, v and the probabilities enter the matrix cores
+    as two-term bf16 splits, softmax and accumulation in fp32, an IEEE division at the end.  Opt-in through the attention
+    modules' ``attention_mfma16_fp32`` flag."""
+    assert q.dtype == torch.float32 and k.dtype == q.dtype and v.dtype == q.dtype
+    assert q.is_contiguous() and k.is_contiguous() and v.is_contiguous()
+    B, T, _ = q.shape
+    S = k.shape[1]
+    o = torch.empty_like(q)
+
+    def issue():
+        _lib_call("dgq_attention_mfma16_f32", _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), B, H, T, S, D, _c.c_float(scale), _lib.stream())
+    issue()
+    if ATTN_LAUNCH_HOOK is not None:                   # the accounting of ``attention``
+        ATTN_LAUNCH_HOOK(issue, 4.0 * T * S * D * B * H, (2 * B * T + 2 * B * S) * H * D * q.element_size())
+    return o
+
+
 def attention_sync_timeouts():
     """Workgroups of single-launch attention calls (csrc/attn_one.hip) that ever gave up the wait for the real-time δ exchange
     in this process; synchronises.  0 unless a grid was not resident as a whole."""

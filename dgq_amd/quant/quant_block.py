@@ -394,6 +394,12 @@ def quant_attention_forward(attn, hidden_states, encoder_hidden_states=None, res
     # weight reconstruction (reconstruction.py) differentiates through the block: the fused kernels have no backward, so a
     # forward that records a graph takes the materialised torch formulation below
     needs_grad = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad)
+    if (not use_aq and getattr(attn, "attention_mfma16_fp32", False) and q.is_cuda and q.dtype == k.dtype == v.dtype == torch.float32
+            and D in ops.ATTN_HEAD_DIMS and not needs_grad):
+        # opt-in (QuantModel.set_attention_mfma16_fp32): the un-quantised attention of the fp32 state in one launch on the bf16 matrix
+        # cores (two-term bf16 splits, fp32 softmax: DESIGN.md §8) instead of the exact fp32 MFMA kernel below
+        o = ops.attention_mfma16_f32(q.contiguous(), k.contiguous(), v.contiguous(), H, D, float(attn.scale))
+        return _attn_out(attn, o, residual)
     if (D in ops.ATTN_HEAD_DIMS and q.is_cuda and q.dtype == k.dtype == v.dtype and not needs_grad
             and (q.dtype == torch.float32
                  or (q.dtype in ops.FLOAT_DTYPES and use_aq and ops.attention_fuses_fakequant(D, mode_w)))):

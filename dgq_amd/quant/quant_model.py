@@ -123,6 +123,18 @@ class QuantModel(nn.Module):
                 for attn in (m.attn1, m.attn2):
                     attn.attention_mfma16 = bool(flag)
 
+    def set_attention_mfma16_fp32(self, flag: bool = True) -> None:
+        """Opt in to (or out of) dgq_attention_mfma16_f32 on every attention the quant blocks drive (their ``attention_mfma16_fp32``
+        flag): with activation quantisation off, attention on fp32 tensors runs in one launch on the bf16 matrix cores (two-term bf16
+        splits) instead of the exact fp32 MFMA kernel.  Off by default: the result differs from the exact kernel's by the split's
+        rounding.  A switch of its own — ``set_attention_mfma16`` leaves the fp32 state alone; the quantised modes, the
+        16-bit states and the CPU never read this flag."""
+        self._drop_graphs()
+        for m in self.model.modules():
+            if isinstance(m, QuantBasicTransformerBlock):
+                for attn in (m.attn1, m.attn2):
+                    attn.attention_mfma16_fp32 = bool(flag)
+
     def disable_out_quantization(self) -> None:
         """conv_in / conv_out stay floating point (quant_model.py:118-124)."""
         self._drop_graphs()

@@ -46,7 +46,8 @@ extern "C" {
  *        entry or struct changed (a binding written against 123 keeps working): the real-time per-row activation quantiser tables,
  *        dgq_act_row_params / dgq_act_row_params_batch with their dgq_act_rowparams_out_t; the real-time block mode,
  *        dgq_quant_act_block / dgq_dequant_act_block / dgq_gemm_blockq with dgq_act_block_out_t and dgq_gemm_block_t; dgq_conv2d_wq_mfma16 (the weight-only
- *        state on the 16-bit matrix cores); dgq_attention_mfma16 (un-quantised attention of the 16-bit states on the same cores) */
+ *        state on the 16-bit matrix cores); dgq_attention_mfma16 (un-quantised attention of the 16-bit states on the same cores);
+ *        dgq_attention_mfma16_f32 (the same for fp32 tensors, every operand a two-term bf16 split) */
 #define DGQ_ABI_VERSION 123
 int dgq_version(void);
 const char* dgq_last_error(void);
@@ -474,6 +475,16 @@ int dgq_attention_sync_timeouts(void);
  * B, H, T, S >= 1 with B·H <= 65535.  Launches on `stream`, allocates nothing, does not synchronise. */
 int dgq_attention_mfma16(const void* q, const void* k, const void* v, void* o, int dtype, int B, int H, int T, int S, int D,
                          float scale, void* stream);
+
+/* dgq_attention_mfma16_f32: the same attention on fp32 tensors, still on the bf16 matrix cores, in ONE launch with no workspace
+ * (csrc/attn_mfma16_split.hip).  Every fp32 operand enters as its two-term bf16 split hi = bf16_rn(x), lo = bf16_rn(x − hi):
+ * s_j = scale·fp32(Σ_d q_lo·k_hi + q_hi·k_lo + q_hi·k_hi), online softmax in fp32 as above (l sums the unrounded p_j),
+ * acc += p_lo·v_hi + p_hi·v_lo + p_hi·v_hi, o = acc / l with an IEEE division; the lo·lo terms are dropped.  Per element
+ * |o − o64| <= (2E + 2^-15)·Σ_j p_j|v_j| + 2^-24·|o64|, E = (3·2^-18 + 3·D·2^-24)·|scale|·max_j Σ_d |q_d·k_{j,d}|.
+ * Layout, head dims, geometry limits and alignment of dgq_attention_mfma16; fp32 tensors keep dgq_attention (mode 0, the exact fp32
+ * MFMA) unless a caller asks for this entry.  Launches on `stream`, allocates nothing, does not synchronise. */
+int dgq_attention_mfma16_f32(const float* q, const float* k, const float* v, float* o, int B, int H, int T, int S, int D, float scale,
+                             void* stream);
 
 /* ---- batched small-M Linear ------------------------------------------------------------------------
  * dgq_linear_smallm_batch: y_l = W_l·aqtizer_l(act(x)) + b_l for up to 24 quantized Linear layers that share one input
