@@ -20,9 +20,19 @@ __device__ __forceinline__ Moments merge(Moments a, Moments b) {
     return r;
 }
 
+// Σ v over the 16 lanes of a DPP row, in every lane: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror — four
+// VALU moves, no LDS traffic.  All 64 lanes must be active.
+__device__ __forceinline__ float row16_sum(float v) {
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));
+    return v;
+}
+
 // grid (B*G, S): block handles spatial rows [s*rows_per, ...) of group g of image b.  Per thread: shifted sums
-// Σ(x − K), Σ(x − K)² with K = the first element of the block's range (3 VALU per element, no cancellation worth
-// mentioning because K sits inside the data), converted to (n, mean, M2) and merged pairwise (Chan) in a fixed order.
+// Σ(x − K), Σ(x − K)² with K = the mean of the first elements of the thread's 16-lane row (3 VALU per element, no cancellation
+// worth mentioning because K sits in the middle of the data), converted to (n, mean, M2) and merged pairwise (Chan) in a fixed order.
 // S == 1 (FINAL): the block also writes the group's scale/shift, so the whole GroupNorm statistic is one launch.
 template <typename T, bool FINAL>
 __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x, int HW, int C, int G, int rows_per,
@@ -33,12 +43,26 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
     const int Cg = C / G;
     const int r0 = blockIdx.y * rows_per, r1 = min(HW, r0 + rows_per);
     const T* base = x + ((int64_t)b * HW) * C + g * Cg;
-    const float K = dgq_to_float(base[(int64_t)r0 * C]);
     const int total = (r1 - r0) * Cg;
     float s1 = 0.0f, s2 = 0.0f, cnt = 0.0f;
-    int r = threadIdx.x / Cg, c = threadIdx.x - r * Cg;     // element i = r*Cg + c, advanced by 256 without divisions
+    // K: the mean of the first elements of the 16 lanes of a DPP row.  A single element as K — the range's first, as before — fails
+    // when that element is an outlier: at 100 sigma every d is ~100 sigma and s2 − s1·md cancels in all 256 threads (measured rho 27
+    // .. 8553 against float64 where fp32 F.group_norm has 1 .. 4, profiles/r16_groupnorm_stats.txt); in a mean of 16 the same outlier
+    // moves K by 6 sigma, in the 16 threads of one row.  Lanes past the range take its last element, so every row averages 16 values
+    // and equal values give exactly that value (the sum and the division by 16 are exact: a constant group keeps M2 == 0).
+    const bool live = (int)threadIdx.x < total;
+    const int e0 = min((int)threadIdx.x, total - 1);
+    int r = e0 / Cg, c = e0 - r * Cg;                       // element i = r*Cg + c, advanced by 256 without divisions
     const int dr = 256 / Cg, dc = 256 - dr * Cg;
-    for (int i = threadIdx.x; i < total; i += 256) {
+    const float x0 = dgq_to_float(base[(int64_t)(r0 + r) * C + c]);
+    const float K = row16_sum(x0) * 0.0625f;
+    if (live) {
+        const float d = x0 - K;
+        s1 = d; s2 = d * d; cnt = 1.0f;
+        r += dr; c += dc;
+        if (c >= Cg) { c -= Cg; ++r; }
+    }
+    for (int i = threadIdx.x + 256; i < total; i += 256) {
         const float d = dgq_to_float(base[(int64_t)(r0 + r) * C + c]) - K;
         s1 += d;
         s2 += d * d;
