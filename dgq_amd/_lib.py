@@ -52,6 +52,10 @@ SIGNATURES = {
     "dgq_quant_act_block": [_vp, _vp, _vp],
     "dgq_dequant_act_block": [_vp, _vp, _i, _i64, _i, _vp, _i, _vp],
     "dgq_gemm_blockq": [_vp, _vp, _vp],
+    "dgq_quant_act_mx6": [_vp, _vp, _vp],
+    "dgq_dequant_act_mx6": [_vp, _vp, _i, _i64, _i, _vp, _i, _vp],
+    "dgq_pack_w_mx6": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "dgq_gemm_mx6": [_vp, _vp, _vp],
     "dgq_gemm_wxa8_batch": [_i, _vp, _vp],
     "dgq_adaround_soft_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
     "dgq_adaround_soft_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
@@ -111,6 +115,17 @@ class ActBlockOut(ctypes.Structure):
 class GemmBlock(ctypes.Structure):
     """dgq_gemm_block_t of include/dgq_hip.h"""
     _fields_ = [("table", _vp), ("ldt", _i), ("vc", _vp), ("B", _i), ("H", _i), ("W", _i), ("C", _i), ("kh", _i), ("kw", _i),
+                ("stride", _i), ("pad", _i), ("ups", _i)]
+
+
+class ActMx6Out(ctypes.Structure):
+    """dgq_act_mx6_out_t of include/dgq_hip.h"""
+    _fields_ = [("codes", _vp), ("scale", _vp), ("lds", _i)]
+
+
+class GemmMx6(ctypes.Structure):
+    """dgq_gemm_mx6_t of include/dgq_hip.h"""
+    _fields_ = [("scale", _vp), ("lds", _i), ("B", _i), ("H", _i), ("W", _i), ("C", _i), ("kh", _i), ("kw", _i),
                 ("stride", _i), ("pad", _i), ("ups", _i)]
 
 

@@ -51,6 +51,9 @@ def parse_args(argv=None):
     p.add_argument("--aq_real_time_block", type=int, default=0,
                    help="with --aq_real_time: 32 = one pair per row and block of 32 consecutive channels (dgq_quant_act_block + "
                         "dgq_gemm_blockq); 0 = one pair per row")
+    p.add_argument("--aq_real_time_format", default="int", choices=("int", "mxfp6"),
+                   help="with --aq_real_time --aq_real_time_block 32 and 6 activation bits: mxfp6 = every block one power-of-two scale and "
+                        "32 FP6 E2M3 codes on the block-scaled matrix cores (dgq_quant_act_mx6 + dgq_gemm_mx6; W4 layers, W4A6)")
     p.add_argument("--wq_mfma16", action="store_true",
                    help="weight-only state (no --use_aq): run the layers on the bf16 / f16 matrix cores (dgq_conv2d_wq_mfma16) — faster, "
                         "not bit-identical to the default exact route")
@@ -80,6 +83,9 @@ def main(argv=None):
         raise SystemExit("--aq_real_time_block is a granularity of the real-time mode: it needs --use_aq --aq_real_time")
     if opt.aq_real_time_block not in (0, 32):
         raise SystemExit("--aq_real_time_block is 0 or 32")
+    if opt.aq_real_time_format == "mxfp6" and not (opt.use_aq and opt.aq_real_time and opt.aq_real_time_block == 32 and opt.aq == 6):
+        raise SystemExit("--aq_real_time_format mxfp6 is a format of the real-time block mode at 6 activation bits: it needs --use_aq "
+                         "--aq_real_time --aq_real_time_block 32 and --aq 6")
     logging.basicConfig(level=logging.INFO)
     from .diffusers_rewrite import UNet2DConditionModel, ARCH
     from .quant import get_qmodel, Scaler
@@ -123,6 +129,8 @@ def main(argv=None):
         aq_params["real_time"] = True
         if opt.aq_real_time_block:
             aq_params["real_time_block"] = opt.aq_real_time_block
+        if opt.aq_real_time_format != "int":
+            aq_params["real_time_format"] = opt.aq_real_time_format
     softmax_aq_params = {"softmax_a_bit": opt.aq, "t2i_log_quant": opt.t2i_log_quant,
                          "t2i_real_time": opt.t2i_real_time, "t2i_start_peak": opt.t2i_start_peak, "log_max_1": False}
     time_aware = opt.time_aware_aqtizer if opt.use_aq else False

@@ -161,6 +161,27 @@ class PackedWeight:
         self._vn = None
         self._vc = None
         self._mfma16 = None
+        self._mx6 = None
+        self._mx6_ok = None
+
+    @property
+    def mx6_eligible(self):
+        """True when dgq_gemm_mx6 may take this weight: W4, integer zero points and |q − z| <= 15 (the arithmetic of check_mfma16), so
+        that every (q − z)/2 is an FP6 E2M3 value.  Computed once per packed weight."""
+        if self._mx6_ok is None:
+            self._mx6_ok = self.bits == 4 and self.check_mfma16(self.codes, self.zp_true, 4)
+        return self._mx6_ok
+
+    def mx6(self):
+        """(image, Kp): the E2M3 codes of (q − z)/2 in the natural K order, [N][Kp/32][24] bytes (dgq_pack_w_mx6) — cached, one extra
+        image per layer at 0.75 bytes per weight"""
+        if self._mx6 is None:
+            assert self.mx6_eligible, "PackedWeight.mx6: W4 with integer zero points and |q - z| <= 15"
+            Kp = round_up(self.K, KTILE)
+            img = torch.empty((self.N, Kp // 32, 24), dtype=torch.uint8, device=self.codes.device)
+            _lib_call("dgq_pack_w_mx6", _lib.ptr(self.codes), _lib.ptr(self.zp_true), self.N, self.C, self.taps, Kp, _lib.ptr(img), _lib.stream())
+            self._mx6 = (img, Kp)
+        return self._mx6
 
     def mfma16_eligible(self):
         """True when dgq_conv2d_wq_mfma16 may take this weight: the zero points are integers and every q − z fits the bound (15 for
@@ -219,6 +240,8 @@ class ActBinding:
     dynamic = False
     #: True on a BlockActBinding (see there): the layer runs dgq_quant_act_block + dgq_gemm_blockq
     block = False
+    #: True on a MxActBinding (a block binding; see there): the layer runs dgq_quant_act_mx6 + dgq_gemm_mx6
+    mx = False
 
     def _table(self, key, make):
         if key not in self._koff:
@@ -365,6 +388,26 @@ class BlockActBinding(ActBinding):
         self.L = 0
         self.gamma = pw.bias
         self.vc = pw.vc()
+
+
+class MxActBinding(BlockActBinding):
+    """The binding of a real-time MXFP6 activation quantizer (UniformAffineQuantizer(real_time=True, real_time_block=32,
+    real_time_format="mxfp6")) on a layer whose weight is exact in FP6 E2M3 (PackedWeight.mx6_eligible): the MX weight image, bias and δw —
+    no tables, no timestep slots, one binding per layer.  The routes of a block binding run it as dgq_quant_act_mx6 on the layer INPUT
+    (once per row / pixel: 24 code bytes and one E8M0 scale byte per 32-channel block) + dgq_gemm_mx6."""
+
+    mx = True
+
+    def __init__(self, pw: PackedWeight):
+        assert pw.C % 32 == 0, "real-time MXFP6 quantizer: C % 32 == 0"
+        self.mode, self.abits, self.offset = "block", 6, 0.0
+        self.pw = pw
+        self.wpacked, self.Kp = pw.mx6()
+        self.wfrag = None
+        self.ksrc = None
+        self._koff = {}
+        self.L = 0
+        self.gamma = pw.bias
 
 
 # ------------------------------------------------------------------------------------------ hot path
@@ -941,6 +984,75 @@ def gemm_blockq(q, geom, ab: "BlockActBinding", out_dtype, out=None, extra=None,
     return out
 
 
+def quant_act_mx6(x_cl: torch.Tensor, geom, pre=None, ln=None, ups=False, lds=None):
+    """dgq_quant_act_mx6 on the layer INPUT x_cl (channels-last storage, geom as for quant_act_block): one launch.  Returns (codes uint8
+    [rows][C/32][24], scale uint8 [rows][lds] = E + 127 per 32-channel block) with rows = the input's rows / pixels (the SOURCE pixels
+    with ``ups``); lds (default C/32) > C/32 adds entries of 127 (a Linear layer's K padding).  pre / ln / ups as in quant_act."""
+    B, H, W, C = geom[:4]
+    sh = 1 if ups else 0
+    rows = B * (H >> sh) * (W >> sh)
+    lds = C // 32 if lds is None else lds
+    a, keep = _quant_input(x_cl, geom, 6, pre, ln, ups)
+    codes = torch.empty((rows, C // 32, 24), dtype=torch.uint8, device=x_cl.device)
+    scale = torch.empty((rows, lds), dtype=torch.uint8, device=x_cl.device)
+    o = _lib.ActMx6Out()
+    o.codes, o.scale, o.lds = codes.data_ptr(), scale.data_ptr(), lds
+
+    def issue(_keep=(keep, codes, scale)):
+        _lib_call("dgq_quant_act_mx6", _c.byref(a), _c.byref(o), _lib.stream())
+    issue()
+    if BLOCK_LAUNCH_HOOK is not None:
+        BLOCK_LAUNCH_HOOK(issue, "quant", (rows, C))
+    return codes, scale
+
+
+def dequant_act_mx6(codes, scale, out):
+    """out [rows][C] = x̂ from quant_act_mx6's codes and scales (dgq_dequant_act_mx6)"""
+    rows, C = codes.shape[0], codes.shape[1] * 32
+    _lib_call("dgq_dequant_act_mx6", _lib.ptr(codes), _lib.ptr(scale), scale.shape[1], rows, C, _lib.ptr(out), _lib.DTYPE_CODE[out.dtype],
+              _lib.stream())
+    return out
+
+
+def gemm_mx6(q, geom, ab: "MxActBinding", out_dtype, out=None, extra=None, ups=False):
+    """One dgq_gemm_mx6 launch on q = quant_act_mx6(...) of the layer input; geom = (B, H, W, C, kh, kw, stride, pad) of the layer
+    (H, W: behind a folded upsample).  Returns y [M][N] (N/2 columns with the GEGLU epilogue)."""
+    codes, scale = q
+    B, H, W, C, kh, kw, stride, pad = geom
+    M = B * ((H + 2 * pad - kh) // stride + 1) * ((W + 2 * pad - kw) // stride + 1)
+    pw = ab.pw
+    if out is None:
+        out = torch.empty((M, pw.N // 2 if (extra is not None and extra.geglu) else pw.N), dtype=out_dtype, device=codes.device)
+    g = _lib.GemmArgs()
+    g.codes, g.rowsum_parts = codes.data_ptr(), 1
+    g.M, g.Kp, g.wpacked, g.w_bits, g.N, g.per_m, g.L = M, ab.Kp, ab.wpacked.data_ptr(), 4, pw.N, 0, 1
+    g.alpha, g.gamma = pw.alpha.data_ptr(), ab.gamma.data_ptr()
+    g.y, g.y_dtype, g.ldy = out.data_ptr(), _lib.DTYPE_CODE[out.dtype], out.stride(0)
+    if extra is not None:
+        g.extra = _c.cast(_c.pointer(extra), _c.c_void_p)
+    k = _lib.GemmMx6()
+    k.scale, k.lds = scale.data_ptr(), scale.shape[1]
+    k.B, k.H, k.W, k.C, k.kh, k.kw, k.stride, k.pad, k.ups = B, H, W, C, kh, kw, stride, pad, 1 if ups else 0
+
+    def issue(_keep=(q, out, extra, ab)):
+        _lib_call("dgq_gemm_mx6", _c.byref(g), _c.byref(k), _lib.stream())
+    issue()
+    if BLOCK_LAUNCH_HOOK is not None:
+        BLOCK_LAUNCH_HOOK(issue, "gemm", (M, pw.N, pw.K))
+    return out
+
+
+def _block_quant(ab, x_cl, geom, pre=None, ln=None, ups=False, pad_k=False):
+    """the input of a block binding quantised by its format's entry; pad_k: table / scale entries up to Kp/32 (Linear layers)"""
+    if ab.mx:
+        return quant_act_mx6(x_cl, geom, pre, ln, ups, lds=ab.Kp // 32 if pad_k else None)
+    return quant_act_block(x_cl, geom, ab.abits, pre, ln, ups, ldt=ab.Kp // 32 if pad_k else None)
+
+
+def _block_gemm(ab, q, geom, out_dtype, out=None, extra=None, ups=False):
+    return (gemm_mx6 if ab.mx else gemm_blockq)(q, geom, ab, out_dtype, out=out, extra=extra, ups=ups)
+
+
 def quant_linear(x: torch.Tensor, ab: ActBinding, pre_act=0, residual=None, fq=None, ln=None, geglu=False):
     """x [..., K] -> [..., N].  pre_act: 0 none, 1 SiLU(x), 2 GEGLU (x is [..., 2K]: x[:K]·gelu(x[K:])) folded into the
     quantise-on-load pass; residual [..., N] and fq (see make_extra) folded into the GEMM epilogue.  geglu: the weight rows
@@ -959,7 +1071,7 @@ def quant_linear(x: torch.Tensor, ab: ActBinding, pre_act=0, residual=None, fq=N
             res2 = res2.contiguous()
     if ab.block:                                         # real-time block mode: quantise the rows once, one GEMM
         geom = (rows, 1, 1, K, 1, 1, 1, 0)
-        y = gemm_blockq(quant_act_block(x2, geom, ab.abits, pre, ln, ldt=ab.Kp // 32), geom, ab, x.dtype, extra=make_extra(res2, fq, geglu=geglu))
+        y = _block_gemm(ab, _block_quant(ab, x2, geom, pre, ln, pad_k=True), geom, x.dtype, extra=make_extra(res2, fq, geglu=geglu))
         return y.view(*x.shape[:-1], y.shape[-1])
     ab = _bind_rows(ab, x2, (rows, 1, 1, K, 1, 1, 1, 0), pre, ln)
     if pre_act != 2 and act_fuses(ab, rows, K, x.dtype, x2=x2):
@@ -1009,9 +1121,10 @@ def quant_linear_multi(x: torch.Tensor, bindings, ln=None):
         for i, ab in enumerate(bindings):
             if ab.block:
                 assert ab.pw.K == Kin and ab.pw.taps == 1
-                if ab.abits not in quants:
-                    quants[ab.abits] = quant_act_block(x2, geom, ab.abits, None, ln, ldt=ab.Kp // 32)
-                res[i] = gemm_blockq(quants[ab.abits], geom, ab, x.dtype)
+                fmt = (ab.mx, ab.abits)                 # (one padded K per input width: every binding's Kp / 32 is the same)
+                if fmt not in quants:
+                    quants[fmt] = _block_quant(ab, x2, geom, None, ln, pad_k=True)
+                res[i] = _block_gemm(ab, quants[fmt], geom, x.dtype)
                 res[i] = res[i].view(*x.shape[:-1], res[i].shape[-1])
         rest = [i for i in range(len(bindings)) if i not in res]
         if rest:
@@ -1123,9 +1236,9 @@ def quant_conv2d(x: torch.Tensor, ab: ActBinding, kh, kw, stride, pad, norm=None
         # real-time block mode: every input pixel (the SOURCE pixel of a folded upsample; a pixel's block parameters do not depend on
         # the taps that read it) is quantised once, the GEMM gathers the taps
         geom = (B, H, W, C, kh, kw, stride, pad)
-        q = quant_act_block(x_store, geom, ab.abits, pre, ups=upsample)
+        q = _block_quant(ab, x_store, geom, pre, ups=upsample)
         part = _gn_partial(gn_out, M, N, Ho * Wo, x.device)
-        y = gemm_blockq(q, geom, ab, x.dtype, out=out, extra=extra_with(part), ups=upsample)
+        y = _block_gemm(ab, q, geom, x.dtype, out=out, extra=extra_with(part), ups=upsample)
         return _gn_tagged(y, part, B, Ho, Wo, N)
     if kh == 1 and kw == 1 and stride == 1 and pad == 0 and act_fuses(ab, M, C, x.dtype, x2=x_store.reshape(M, C)):
         # a 1x1 convolution is a Linear layer over the pixels: one launch, the GEMM quantises its own rows (dgq_gemm_act_t)

@@ -244,13 +244,16 @@ class QuantBasicTransformerBlock(BaseQuantBlock):
         if (_F_GEGLU_EPI and len(net) == 3 and hasattr(net[0], "proj") and isinstance(net[0].proj, QuantLayer)
                 and net[0].proj.w.shape[0] % 4 == 0):
             net[0].proj.geglu_rows = True                      # packed rows (value, gate) interleaved: see QuantLayer
+        aq_params_qkv = dict(aq_params)
+        aq_params_qkv.pop("real_time_format", None)            # (a layer-side format: the attention-side quantizers keep their integer per-token form)
         for attn in (self.attn1, self.attn2):
-            attn.aqtizer_q = UniformAffineQuantizer(**aq_params)
-            attn.aqtizer_k = UniformAffineQuantizer(**aq_params)
-            attn.aqtizer_v = UniformAffineQuantizer(**aq_params)
+            attn.aqtizer_q = UniformAffineQuantizer(**aq_params_qkv)
+            attn.aqtizer_k = UniformAffineQuantizer(**aq_params_qkv)
+            attn.aqtizer_v = UniformAffineQuantizer(**aq_params_qkv)
         aq_params_w = dict(aq_params)
         aq_params_w.pop("real_time", None)                     # (the layer-side flag: aqtizer_w keeps t2i_log_quant / t2i_real_time)
         aq_params_w.pop("real_time_block", None)
+        aq_params_w.pop("real_time_format", None)
         aq_params_w["bits"] = softmax_aq_params["softmax_a_bit"]
         aq_params_w["symmetric"] = False
         aq_params_w["always_zero"] = True

@@ -178,6 +178,55 @@ def block_minmax(blk_min: torch.Tensor, blk_max: torch.Tensor, level: int):
     return row_minmax(blk_min, blk_max, level)
 
 
+#: E2M3 magnitudes by 5-bit code (exponent << 3 | mantissa): subnormals m/8, then (1 + m/8)·2^(e−1)
+E2M3_MAGNITUDES = tuple(m / 8.0 if e == 0 else (1.0 + m / 8.0) * 2.0 ** (e - 1) for e in range(4) for m in range(8))
+
+
+def mx6_block(rows: torch.Tensor):
+    """The MXFP6 statement dgq_quant_act_mx6 reproduces bit for bit (``real_time_format="mxfp6"``): rows [R][C] fp32 (C % 32 == 0, finite,
+    behind any folded prologue), every 32 consecutive channels one block.  With amax = max |x′| of the block, E = floor(log2 amax) − 2
+    — the OCP MX rule for E2M3 (emax 2), read off the exponent field of amax — clamped to [−127, 127], −127 for amax = 0; v = x′·2^−E (an
+    exact scaling, |v| < 8) is rounded to nearest, ties to even, onto the E2M3 grid (steps 0.125 below 2, 0.25 below 4, 0.5 above) and
+    saturates at ±7.5; a zero magnitude is the code +0.  Returns (codes uint8 [R][C] = sign << 5 | exponent << 3 | mantissa, scale uint8
+    [R][C/32] = E + 127, x̂ fp32 [R][C] = value(code)·2^E)."""
+    x = rows.detach().float()
+    R, C = x.shape
+    assert C % REAL_TIME_BLOCK == 0
+    xb = x.view(R, C // REAL_TIME_BLOCK, REAL_TIME_BLOCK)
+    amax = xb.abs().amax(dim=2)
+    field = (amax.contiguous().view(torch.int32) >> 23) & 0xFF              # 0 for zero and subnormal amax
+    E = torch.clamp(field - 129, min=-127)                                     # (finite amax: at most 125)
+    inv = torch.ldexp(torch.ones_like(amax), -E)                               # 2^−E, a normal float
+    v = xb * inv[:, :, None]
+    a = v.abs()
+    step = torch.where(a < 2.0, torch.full_like(a, 0.125), torch.where(a < 4.0, torch.full_like(a, 0.25), torch.full_like(a, 0.5)))
+    q = torch.clamp(torch.round(a / step) * step, max=7.5)                     # torch.round: half to even; a / step is exact
+    qe = torch.floor(torch.log2(torch.clamp(q, min=1.0))).to(torch.int32)      # 0, 1, 2 for the normal ranges (exact at powers of two)
+    mag = torch.where(q < 1.0, (q * 8.0).to(torch.int32), ((qe + 1) << 3) | ((q / torch.ldexp(torch.ones_like(q), qe) - 1.0) * 8.0).to(torch.int32))
+    sign = torch.where((v < 0) & (mag > 0), 32, 0).to(torch.int32)
+    codes = (mag | sign).to(torch.uint8).view(R, C)
+    xhat = (torch.where(v < 0, -q, q) * torch.ldexp(torch.ones_like(amax), E)[:, :, None]).view(R, C)
+    return codes, (E + 127).to(torch.uint8), xhat
+
+
+def mx6_pack(codes: torch.Tensor):
+    """6-bit codes [R][C] (uint8) -> [R][C/32][24] bytes: element j of a block at bits 6j .. 6j + 5 of its 192-bit little-endian string
+    (four codes per three bytes) — the FP6 operand image"""
+    R, C = codes.shape
+    c = codes.view(R, C // 4, 4).to(torch.int32)
+    w = c[..., 0] | (c[..., 1] << 6) | (c[..., 2] << 12) | (c[..., 3] << 18)
+    out = torch.stack([w & 0xFF, (w >> 8) & 0xFF, (w >> 16) & 0xFF], dim=-1).to(torch.uint8)
+    return out.view(R, C // REAL_TIME_BLOCK, 24)
+
+
+def mx6_unpack(packed: torch.Tensor):
+    """inverse of ``mx6_pack``: [R][C/32][24] bytes -> codes uint8 [R][C]"""
+    R = packed.shape[0]
+    b = packed.reshape(R, -1, 3).to(torch.int32)
+    w = b[..., 0] | (b[..., 1] << 8) | (b[..., 2] << 16)
+    return torch.stack([(w >> (6 * j)) & 63 for j in range(4)], dim=-1).to(torch.uint8).view(R, -1)
+
+
 def group_params_from_ranges(in_min, in_max, out_min, out_max, group_num, mode, level, force_in_channel=None):
     """The host half of ``done_group_num`` (quant_layer.py:338-418) as a pure function of the folded range vectors —
     returns (δ, z, in_channel_wise) in the checkpoint's broadcast shapes.  Arithmetic follows the reference line by
@@ -234,11 +283,15 @@ class UniformAffineQuantizer(nn.Module):
     (``block_minmax``), so an outlier sets the step of its own 32 channels only.  A convolution row has, for every tap, the C/32 blocks
     of that tap's input pixel (a tap outside the image is a block of zeros and contributes exactly 0), so its input is quantised
     once per pixel (dgq_quant_act_block + dgq_gemm_blockq).  Layers with C % 32 != 0 and the attention-side quantizers keep the
-    per-row / per-token form."""
+    per-row / per-token form.
+
+    ``real_time_format="mxfp6"`` (with ``real_time_block=32`` and 6 bits): the block is an OCP MXFP6 block instead — one power-of-two
+    scale and 32 FP6 E2M3 codes (``mx6_block``), the operand of the block-scaled matrix cores (dgq_quant_act_mx6 + dgq_gemm_mx6).  W4
+    layers with integer zero points and C % 32 == 0 take it; every other layer runs as with ``real_time_block=32`` alone."""
 
     def __init__(self, bits: int = 8, symmetric: bool = False, channel_wise: bool = False,
                  scaler: Scaler = Scaler.MINMAX, leaf_param: bool = False, always_zero: bool = False,
-                 quant_emb: bool = False, real_time: bool = False, real_time_block: int = 0) -> None:
+                 quant_emb: bool = False, real_time: bool = False, real_time_block: int = 0, real_time_format: str = "int") -> None:
         super().__init__()
         if symmetric:
             raise NotImplementedError("symmetric quantizers are not used by the DGQ inference path")
@@ -247,8 +300,13 @@ class UniformAffineQuantizer(nn.Module):
         if real_time_block not in (0, REAL_TIME_BLOCK) or (real_time_block and not real_time):
             raise ValueError("real_time_block is 0 (one pair per row) or %d (one pair per row and block of %d consecutive channels), and a "
                              "granularity of real_time=True" % (REAL_TIME_BLOCK, REAL_TIME_BLOCK))
+        if real_time_format not in ("int", "mxfp6"):
+            raise ValueError("real_time_format is \"int\" or \"mxfp6\", not %r" % (real_time_format,))
+        if real_time_format == "mxfp6" and not (real_time and real_time_block == REAL_TIME_BLOCK and bits == 6):
+            raise ValueError("real_time_format=\"mxfp6\" is a format of real_time=True with real_time_block=%d and bits=6" % REAL_TIME_BLOCK)
         self.real_time = bool(real_time)
         self.real_time_block = int(real_time_block)
+        self.real_time_format = real_time_format
         self.level = 2 ** bits
         self.symmetric = symmetric
         self.channel_wise = channel_wise
@@ -392,6 +450,11 @@ class UniformAffineQuantizer(nn.Module):
                 # block form: the new quantiser's codes and {δ, β} tables, then a dequantise
                 if x.shape[-1] % self.real_time_block != 0:
                     raise NotImplementedError("stand-alone real-time block quantizer: [..., C] inputs with C %% %d == 0" % self.real_time_block)
+                if self.real_time_format == "mxfp6":
+                    codes, scale = ops.quant_act_mx6(x2d, (x2d.shape[0], 1, 1, x2d.shape[1], 1, 1, 1, 0))
+                    out = torch.empty_like(xc)
+                    ops.dequant_act_mx6(codes, scale, out.view(x2d.shape))
+                    return out
                 codes, table, _rho = ops.quant_act_block(x2d, (x2d.shape[0], 1, 1, x2d.shape[1], 1, 1, 1, 0), self.bits)
                 out = torch.empty_like(xc)
                 ops.dequant_act_block(codes, table, out.view(x2d.shape))
@@ -415,7 +478,8 @@ class UniformAffineQuantizer(nn.Module):
     def extra_repr(self) -> str:
         return "level=%d, channel_wise=%s, leaf_param=%s, always_zero=%s%s" % (
             self.level, self.channel_wise, self.leaf_param, self.always_zero,
-            (", real_time=True" + (", real_time_block=%d" % self.real_time_block if self.real_time_block else "")) if self.real_time else "")
+            (", real_time=True" + (", real_time_block=%d" % self.real_time_block if self.real_time_block else "")
+             + (", real_time_format=%s" % self.real_time_format if self.real_time_format != "int" else "")) if self.real_time else "")
 
     def half(self):
         super().half()
@@ -616,9 +680,14 @@ class QuantLayer(nn.Module):
         if self.aqtizer.real_time:                # no tables, no slots: one natural-order binding, its row tables made per call
             if "real_time" not in self._bindings:
                 # block granularity where the input channels split into whole 32-blocks; the per-row mode otherwise
+                # (MXFP6 blocks where the format asks for them and the weight is exact in E2M3)
                 blk = self.aqtizer.real_time_block
-                self._bindings["real_time"] = (ops.BlockActBinding(pw, self.aqtizer.bits) if blk and self.in_channels % blk == 0
-                                               else ops.DynamicActBinding(pw, self.aqtizer.bits))
+                whole = blk and self.in_channels % blk == 0
+                if whole and self.aqtizer.real_time_format == "mxfp6" and pw.mx6_eligible:
+                    self._bindings["real_time"] = ops.MxActBinding(pw)
+                else:
+                    self._bindings["real_time"] = (ops.BlockActBinding(pw, self.aqtizer.bits) if whole
+                                                   else ops.DynamicActBinding(pw, self.aqtizer.bits))
             return self._bindings["real_time"]
         slot = self._slot_ref.slot if self._slot_ref is not None else None
         if slot is not None and slot in self._act_tables:

@@ -47,7 +47,8 @@ extern "C" {
  *        dgq_act_row_params / dgq_act_row_params_batch with their dgq_act_rowparams_out_t; the real-time block mode,
  *        dgq_quant_act_block / dgq_dequant_act_block / dgq_gemm_blockq with dgq_act_block_out_t and dgq_gemm_block_t; dgq_conv2d_wq_mfma16 (the weight-only
  *        state on the 16-bit matrix cores); dgq_attention_mfma16 (un-quantised attention of the 16-bit states on the same cores);
- *        dgq_attention_mfma16_f32 (the same for fp32 tensors, every operand a two-term bf16 split) */
+ *        dgq_attention_mfma16_f32 (the same for fp32 tensors, every operand a two-term bf16 split); the real-time MXFP6 mode,
+ *        dgq_quant_act_mx6 / dgq_dequant_act_mx6 / dgq_pack_w_mx6 / dgq_gemm_mx6 with dgq_act_mx6_out_t and dgq_gemm_mx6_t */
 #define DGQ_ABI_VERSION 123
 int dgq_version(void);
 const char* dgq_last_error(void);
@@ -400,6 +401,38 @@ typedef struct dgq_gemm_block {
     int B, H, W, C, kh, kw, stride, pad, ups;
 } dgq_gemm_block_t;
 int dgq_gemm_blockq(const dgq_gemm_args_t* g, const dgq_gemm_block_t* blk, void* stream);
+
+/* ---- real-time MXFP6 activations on the block-scaled matrix cores (W4A6; a mode of this library) -------------------------------------
+ * Every block of DGQ_KCHUNK = 32 consecutive channels of every input row gets ONE power-of-two scale 2^E and 32 FP6 E2M3 codes (sign, 2
+ * exponent bits of bias 1, 3 mantissa bits: magnitudes 0 .. 0.875 and 1 .. 1.875 in steps of 0.125, 2 .. 3.75 of 0.25, 4 .. 7.5 of 0.5).
+ * With amax = max |x′| of the block: E = floor(log2 amax) − 2 (the exponent field of amax; the OCP MX rule with E2M3's emax = 2), clamped
+ * to [−127, 127], E = −127 for amax = 0; code = x′·2^−E rounded to nearest, ties to even, onto the grid, saturating at ±7.5 (a zero
+ * magnitude is stored +0); x̂ = code·2^E.  The statement is dgq_amd/quant/quant_layer.py mx6_block.
+ * dgq_quant_act_mx6: `in` is read exactly as by dgq_quant_act_block (x, x_dtype, B, H, W, C, the folded prologue, ups; C % 32 == 0, x
+ * 16-byte aligned; kh, kw tell a Linear input from a convolution's; bits is only range-checked).  ONE launch, no atomics, capture-safe:
+ *   codes [rows][C/32][24 bytes], 16-byte aligned: element j of a block at bits 6j .. 6j + 5 of its 192-bit little-endian string — the
+ *         FP6 operand image of V_MFMA_SCALE_F32_32X32X64_F8F6F4;
+ *   scale [rows][lds] E8M0 bytes E + 127, lds >= C/32; entries C/32 .. lds − 1 are written 127.
+ * dgq_dequant_act_mx6: y [rows][C] (y_dtype) = x̂ from such codes and scales — the quantizer's stand-alone fake-quant form.
+ * dgq_pack_w_mx6: the weight image of dgq_gemm_mx6 from the integer codes [N][C·taps] (reference order k = c·taps + tap) and the zero
+ * points zw [N] (integers; |q − z| <= 15 — the caller's check): packed [N][Kp/32][24 bytes] = the E2M3 codes of (q − z)/2, each a grid
+ * value, K in the natural order kp = tap·C + c, the K padding up to Kp (a multiple of DGQ_KTILE) as code 0.
+ * dgq_gemm_mx6: y[m,n] = gamma[n] + alpha[n]·Σ_c 2^(E[m,c]+1)·Σ_{k∈c} a[m,k]·w6[n,k], every K step one block-scaled MFMA (activations
+ * the A operand under their own scale bytes, weights the B operand under the constant byte 128), ONE fp32 accumulator over the whole K,
+ * no K split, nothing exchanged between workgroups.  Rows, chunks, taps, ups and the Linear case as for dgq_gemm_blockq (a tap outside
+ * the image contributes exactly 0).  Of `g` are read: codes (= the quantiser's codes), M, Kp, wpacked (dgq_pack_w_mx6), N, alpha (= δw),
+ * gamma (= bias), y, y_dtype, ldy and extra (as for dgq_gemm_blockq; conv and act must be NULL); everything else is ignored. */
+typedef struct dgq_act_mx6_out {
+    uint8_t* codes; uint8_t* scale; int lds;
+} dgq_act_mx6_out_t;
+int dgq_quant_act_mx6(const dgq_quant_act_args_t* in, const dgq_act_mx6_out_t* out, void* stream);
+int dgq_dequant_act_mx6(const uint8_t* codes, const uint8_t* scale, int lds, int64_t rows, int C, void* y, int y_dtype, void* stream);
+int dgq_pack_w_mx6(const uint8_t* codes, const float* zw, int N, int C, int taps, int Kp, uint8_t* packed, void* stream);
+typedef struct dgq_gemm_mx6 {
+    const uint8_t* scale; int lds;    /* dgq_act_mx6_out_t.scale / lds */
+    int B, H, W, C, kh, kw, stride, pad, ups;
+} dgq_gemm_mx6_t;
+int dgq_gemm_mx6(const dgq_gemm_args_t* g, const dgq_gemm_mx6_t* mx, void* stream);
 /* Small tile grids are split along K (deterministic: fp32 partial slabs [S][M][N] in the caller's `workspace`,
  * summed in a fixed order by a second kernel). dgq_gemm_workspace_bytes returns what the preferred split of a
  * shape needs; with workspace == NULL (or too small) fewer / no splits are used — results do not depend on it
