@@ -266,6 +266,9 @@ static int attention_impl(const void* q_, const void* k_, const void* v_, void* 
     DGQ_CHECK_ARG(B > 0 && H > 0 && T > 0 && S > 0, "dgq_attention_f32: bad shape");
     DGQ_CHECK_ARG(mode >= 0 && mode <= 3 && skip >= 0 && skip < S && bits >= 2 && bits <= 8, "dgq_attention_f32: bad mode");
     DGQ_CHECK_ARG(mode < 2 || delta_in, "dgq_attention_f32: static modes need delta");
+    // the quantised kernels keep their running maxima over the UNSCALED scores (attn3_stats_kernel): the order of the scores must be
+    // that of the products.  Mode 0 multiplies before the maximum and takes any finite scale.
+    DGQ_CHECK_ARG(mode == 0 || (scale > 0.0f && scale <= 3.402823466e38f), "dgq_attention_f32: the quantised modes need a finite scale > 0 (scale=%g)", (double)scale);
     hipStream_t st = (hipStream_t)stream;
     AttnF32Params p;
     p.q = q; p.k = k; p.v = v; p.o = o; p.B = B; p.H = H; p.T = T; p.S = S; p.scale = scale; p.mode = mode; p.skip = skip;

@@ -466,7 +466,8 @@ int dgq_logquant_f32(const float* p, float* y, int64_t rows, int S, int skip_col
  * skip = 1 bypasses key column 0 (start_peak, sd.py:191-195).  workspace: caller-owned, 256-byte aligned,
  * >= dgq_attention_workspace_bytes(...) (δ scalar, per-row softmax statistics, bf16 split planes of K and V).
  * head_dim D ∈ {8,16,40,64,80,160}.  Quantised modes run on the bf16 MFMA with exact three-way bf16 operand splits
- * (fp32-equivalent accuracy); mode 0 on the exact fp32 MFMA.
+ * (fp32-equivalent accuracy); mode 0 on the exact fp32 MFMA.  The quantised modes keep their running maxima over the
+ * unscaled scores and need a finite scale > 0 (DGQ_EINVAL before any launch otherwise); mode 0 takes any finite scale.
  * fq (optional, NULL = none): the aqtizer_q / aqtizer_k / aqtizer_v fake-quantizers (sd.py:165-181) applied to the
  * operands as they are loaded, fq[0..2] = q, k, v, each addressed exactly like dgq_fakequant_rows (mode 0 scalar,
  * 1 per token with entry t − skip, 2 per head-dim element; mode < 0 = none for that operand; tokens < skip pass
