@@ -511,7 +511,7 @@ int dgq_attention_mfma16(const void* q, const void* k, const void* v, void* o, i
                          float scale, void* stream);
 
 /* dgq_attention_mfma16_f32: the same attention on fp32 tensors, still on the bf16 matrix cores, in ONE launch with no workspace
- * (csrc/attn_mfma16_split.hip).  Every fp32 operand enters as its two-term bf16 split hi = bf16_rn(x), lo = bf16_rn(x − hi):
+ * (csrc/attn_mfma16.hip, the same kernel body).  Every fp32 operand enters as its two-term bf16 split hi = bf16_rn(x), lo = bf16_rn(x − hi):
  * s_j = scale·fp32(Σ_d q_lo·k_hi + q_hi·k_lo + q_hi·k_hi), online softmax in fp32 as above (l sums the unrounded p_j),
  * acc += p_lo·v_hi + p_hi·v_lo + p_hi·v_hi, o = acc / l with an IEEE division; the lo·lo terms are dropped.  Per element
  * |o − o64| <= (2E + 2^-15)·Σ_j p_j|v_j| + 2^-24·|o64|, E = (3·2^-18 + 3·D·2^-24)·|scale|·max_j Σ_d |q_d·k_{j,d}|.

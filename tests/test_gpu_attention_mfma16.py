@@ -110,6 +110,20 @@ def test_uniform_attention_counts_exactly_S_keys(case, dtype):
     _assert_equal(_run(q, k, v, H, D, scale), want, "uniform")
 
 
+@gpu
+@dtypes
+@cases
+def test_the_32_key_form_is_a_gather_and_counts_too(case, dtype, monkeypatch):
+    """the form the entry does not take by default below D = 160 (DGQ_ATTN16_KT=32, read per call) stays measurable only while it stays
+    right"""
+    D, T, S, H = case
+    monkeypatch.setenv("DGQ_ATTN16_KT", "32")
+    q, k, v, scale, want = ar.onehot_case(case, dtype)
+    _assert_equal(_run(q, k, v, H, D, scale), want, "one-hot, 32-key stages")
+    q, k, v, scale, want = ar.uniform_case(case, dtype)
+    _assert_equal(_run(q, k, v, H, D, scale), want, "uniform, 32-key stages")
+
+
 # ------------------------------------------------------------------------------------------------------------- 6. random data
 @gpu
 @dtypes

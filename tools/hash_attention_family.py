@@ -2,6 +2,9 @@
 every path of attn3_stats_kernel / attn3_pv_kernel / attn3_merge_kernel (csrc/attn_bf16x3.hip) and attn3_one_kernel (csrc/attn_one.hip)
 — their tile bodies are written out twice and must stay equal: the four score forms (QM 0-3), integer and three-plane V, the four softmax modes,
 the three tensor types, ragged tiles and rows, the key split, the 8-wave blocks with one and two tiles per ring stage, one launch.
+A second section does the same for am16_kernel (csrc/attn_mfma16.hip: un-quantised attention on the 16-bit matrix cores, one body for
+16-bit and fp32 tensors) on RANDOM data, where a reordered sum shows: every head dim, ragged T and S, a one-key last stage, 129 stages;
+bf16 / f16 with 64- and 32-key stages, fp32 in its three LDS forms — every instantiated kernel.
 Run it once under each build (DGQ_HIP_LIB=old.so, then the tree's own) and diff the listings.
 usage: python tools/hash_attention_family.py"""
 import hashlib, os, sys
@@ -88,6 +91,26 @@ def main():
                     n += 1
                     j += 1
     print("attention_sync_timeouts %d" % ops.attention_sync_timeouts(), flush=True)
+    mfma16()
+
+
+def mfma16():
+    """ops.attention_mfma16 / ops.attention_mfma16_f32 on the shapes of tests/attention_mfma16_ref.py; q, k ~ N(0, 1.1), v ~ 1.3·N(0, 1) + 0.2"""
+    from tests import attention_mfma16_ref as ar
+    for n, ((D, T, S, H), B) in enumerate([(c, ar.B) for c in ar.CASES] + [(ar.LONG, 1)]):
+        g = torch.Generator().manual_seed(7000 + n)
+        q, k = ((torch.randn(B, m, H * D, generator=g) * 1.1).to(dev) for m in (T, S))
+        v = (1.3 * torch.randn(B, S, H * D, generator=g) + 0.2).to(dev)
+        shape = "D%d T%d S%d H%d B%d" % (D, T, S, H, B)
+        for dt in ("bf16", "f16"):
+            for kt in (None, "32"):
+                env(DGQ_ATTN16_KT=kt)
+                emit("mfma16 %s %s kt%s" % (shape, dt, kt or "-default"), ops.attention_mfma16(q.to(DT[dt]), k.to(DT[dt]), v.to(DT[dt]), H, D, D ** -0.5))
+        env(DGQ_ATTN16_KT=None)
+        for form in ("0", "1", "2"):
+            env(DGQ_ATTN16F_FORM=form)
+            emit("mfma16_f32 %s form%s" % (shape, form), ops.attention_mfma16_f32(q, k, v, H, D, D ** -0.5))
+        env(DGQ_ATTN16F_FORM=None)
 
 
 main()

@@ -1,8 +1,9 @@
 """Parent-against-new table of every kernel of `hipcc -S` listings: VGPRs, AGPRs, SGPRs, scratch bytes, static LDS, wave occupancy (the
 listing's "Kernel info" comments — the figures of the code-object notes tools/check_no_scratch.py reads) and the instruction mix of
 the MFMA loop (as tools/isa_loop.py, but the loop is taken from the listing's loop annotations, so block placement does not move it).  Kernels are paired by demangled name; --drop removes text from the parent's names
-first (a template parameter that went away): --drop "gemm_panel_kernel:, 1, " replaces the first ", 1, " by ", " in that kernel's names.
-usage: python tools/kernel_resources_diff.py parent_dir new_dir file.s [file.s ...] [--drop KERNEL:TEXT ...]"""
+first (a template parameter that went away): --drop "gemm_panel_kernel:, 1, " replaces the first ", 1, " by ", " in that kernel's names;
+--rename rewrites them by a regular expression (kernels that were folded onto another's name): --rename "old_kernel<(.*)>=new_kernel<\\1, Policy>".
+usage: python tools/kernel_resources_diff.py parent_dir new_dir file.s [file.s ...] [--drop KERNEL:TEXT ...] [--rename REGEX=REPL ...]"""
 import re, subprocess, sys
 from collections import Counter
 
@@ -35,7 +36,7 @@ def loop_mix(lines):
     return "%d instr: " % sum(ops.values()) + " ".join("%s=%d" % kv for kv in sorted(ops.items()))
 
 
-def kernels(path, drops):
+def kernels(path, drops, renames=()):
     s = open(path).read()
     out = {}
     for m in re.finditer(r'^(_Z\w+):.*?^; Kernel info:(.*?)^; Occupancy: \d+', s, re.M | re.S):
@@ -48,6 +49,8 @@ def kernels(path, drops):
             kernel, text = d.split(":", 1)
             if kernel in dem:
                 dem = dem.replace(text, ", ", 1)
+        for r in renames:
+            dem = re.sub(*r.split("=", 1), dem)
         res = {k: int(re.search(p, body).group(1)) for k, p in FIELDS}
         res["loop"] = loop_mix(body[:body.index("; Kernel info:")].splitlines())
         out[dem] = res
@@ -55,17 +58,19 @@ def kernels(path, drops):
 
 
 def main():
-    args, drops = [], []
+    args, drops, renames = [], [], []
     it = iter(sys.argv[1:])
     for a in it:
         if a == "--drop":
             drops.append(next(it))
+        elif a == "--rename":
+            renames.append(next(it))
         else:
             args.append(a)
     pdir, ndir, files = args[0], args[1], args[2:]
     ndiff = 0
     for f in files:
-        a, b = kernels("%s/%s" % (pdir, f), drops), kernels("%s/%s" % (ndir, f), [])
+        a, b = kernels("%s/%s" % (pdir, f), drops, renames), kernels("%s/%s" % (ndir, f), [])
         print("== %s: %d kernels (parent), %d (new)" % (f, len(a), len(b)))
         for name in sorted(set(a) | set(b)):
             x, y = a.get(name), b.get(name)
