@@ -37,6 +37,8 @@ SIGNATURES = {
     "dgq_conv2d_f32w": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp],
     "dgq_conv2d_wq": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp],
     "dgq_conv2d_wq_mfma16": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp],
+    "dgq_conv2d_wq_mfma16_fused": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp],
+    "dgq_layernorm_row_stats": [_vp, _i, _i, _i, _f, _vp, _vp],
     "dgq_attention_mfma16": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
     "dgq_attention_mfma16_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],
     "dgq_attention_fuses_fakequant": [_i, _i],
@@ -135,6 +137,12 @@ class GemmArgs(ctypes.Structure):
                 ("N", _i), ("per_m", _i), ("cdelta", _vp), ("cflush", _vp), ("mdelta", _vp), ("mzp", _vp), ("L", _i),
                 ("offset", _f), ("alpha", _vp), ("zw", _vp), ("gamma", _vp), ("vn", _vp), ("y", _vp), ("y_dtype", _i), ("ldy", _i),
                 ("extra", _vp)]
+
+
+class Wq16Fuse(ctypes.Structure):
+    """dgq_wq16_fuse_t of include/dgq_hip.h"""
+    _fields_ = [("pre_scale", _vp), ("pre_shift", _vp), ("ln_stats", _vp), ("ln_gamma", _vp), ("ln_beta", _vp), ("pre_act", _i),
+                ("residual", _vp), ("ldr", _i), ("bias_rows", _vp), ("geglu_out", _i)]
 
 
 class AttnFq(ctypes.Structure):

@@ -57,6 +57,9 @@ def parse_args(argv=None):
     p.add_argument("--wq_mfma16", action="store_true",
                    help="weight-only state (no --use_aq): run the layers on the bf16 / f16 matrix cores (dgq_conv2d_wq_mfma16) — faster, "
                         "not bit-identical to the default exact route")
+    p.add_argument("--wq_fused", action="store_true",
+                   help="with --wq_mfma16: fold GroupNorm / LayerNorm, SiLU, GEGLU, residual adds and the time-embedding rows into the "
+                        "layers' launches (dgq_conv2d_wq_mfma16_fused) instead of torch operators around them — differs by rounding")
     p.add_argument("--attn_mfma16", action="store_true",
                    help="with --fp16 and no --use_aq: run the un-quantised attentions on the f16 matrix cores in one launch "
                         "(dgq_attention_mfma16) instead of matmul / softmax / matmul — faster, differs by rounding")
@@ -70,6 +73,10 @@ def main(argv=None):
     opt = parse_args(argv)
     if opt.wq_mfma16 and opt.use_aq:
         raise SystemExit("--wq_mfma16 selects a route of the weight-only state: it cannot be combined with --use_aq")
+    if opt.wq_fused and opt.use_aq:
+        raise SystemExit("--wq_fused selects a route of the weight-only state: it cannot be combined with --use_aq")
+    if opt.wq_fused and not opt.wq_mfma16:
+        raise SystemExit("--wq_fused folds into the matrix-core layers: it needs --wq_mfma16")
     if opt.attn_mfma16 and opt.use_aq:
         raise SystemExit("--attn_mfma16 selects a route of the un-quantised attention: it cannot be combined with --use_aq")
     if opt.attn_mfma16 and not opt.fp16:
@@ -141,6 +148,8 @@ def main(argv=None):
     qnn.disable_out_quantization()
     if opt.wq_mfma16:
         qnn.set_weight_only_mfma16(True)
+    if opt.wq_fused:
+        qnn.set_weight_only_fused(True)
     if opt.attn_mfma16:
         qnn.set_attention_mfma16(True)
     if opt.attn_mfma16_fp32:

@@ -1361,6 +1361,80 @@ def conv2d_wq_mfma16(x: torch.Tensor, pw: PackedWeight, kh, kw, stride, pad, ups
     return result(y)
 
 
+def layernorm_row_stats(x2d: torch.Tensor, eps):
+    """[rows][2] fp32 (mean, rstd) of the rows of x2d [rows][C] (dgq_layernorm_row_stats: two passes over the row in
+    registers, sums and final arithmetic in fp64, each value rounded to fp32 once) — the ``ln`` input of conv2d_wq_mfma16_fused.  C % 4 == 0 and C <= 2048, else the library refuses."""
+    assert x2d.dim() == 2 and x2d.is_contiguous()
+    rows, C = x2d.shape
+    out = torch.empty((rows, 2), dtype=torch.float32, device=x2d.device)
+    _lib_call("dgq_layernorm_row_stats", _lib.ptr(x2d), _lib.DTYPE_CODE[x2d.dtype], rows, C, _c.c_float(eps), _lib.ptr(out), _lib.stream())
+    return out
+
+
+def layernorm_row_stats_ok(C):
+    """what dgq_layernorm_row_stats accepts (a caller with another width keeps the nn.LayerNorm module)"""
+    return C % 4 == 0 and C <= 2048
+
+
+def _table16(t: torch.Tensor) -> torch.Tensor:
+    """t as a contiguous fp32 table on a 16-byte boundary, as the fused kernel's vector loads of it need: the tensor itself where it
+    already is one (every fresh allocation), else a copy — a γ / β that is a view at an odd offset of a larger buffer"""
+    t = as_f32(t).contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def conv2d_wq_mfma16_fused(x: torch.Tensor, pw: PackedWeight, kh, kw, stride, pad, upsample=False, geglu_rows=False, norm=None, ln=None,
+                           pre_act=0, residual=None, bias_rows=None, geglu=False):
+    """conv2d_wq_mfma16 with the layer's element-wise neighbours folded into the launch (dgq_conv2d_wq_mfma16_fused): operands and
+    returned views as there, and with nothing to fold the same bits.
+    norm: GroupNorm of a 4-D x folded into the load — (groups, eps, gamma, beta, act) as in quant_conv2d (statistics from the partials x
+          carries, else by a pass; act 1 = SiLU behind it), or the fp32 tables themselves, (scale, shift) [B][C];
+    ln:   LayerNorm of a Linear x likewise — (stats, gamma, beta) with stats = layernorm_row_stats(x rows, eps);
+    pre_act 1: SiLU(x) (behind the norm);  residual (the output's shape) and bias_rows [B][N] (one row per image) are added in fp32 before
+    the one rounding — both in the output's column order, with geglu_rows too (the kernel reads them at the column a packed row stands
+    for);  geglu (needs geglu_rows): the result is value·gelu(gate), [..., N/2], bias_rows then [B][N] with the value columns first."""
+    assert pw.mfma16_eligible(), "dgq conv2d_wq_mfma16_fused: q − z is not an integer within the operand's exact range"
+    w_img, Kp = pw.natural()
+    N = pw.N
+    xs, geom, result = _weight_only_operand(x, pw.K, kh, kw, stride, pad, upsample, "conv2d_wq_mfma16_fused")
+    B, H, W = geom[:3]
+    M = B * ((H + 2 * pad - kh) // stride + 1) * ((W + 2 * pad - kw) // stride + 1)
+    f = _lib.Wq16Fuse()
+    keep = []
+    if norm is not None:
+        if len(norm) == 5:
+            sc, sh = _gn_input(x, xs.permute(0, 2, 3, 1), norm)
+            pre_act = int(norm[4])
+        else:
+            sc, sh = (_table16(t) for t in norm)
+        keep += [sc, sh]
+        f.pre_scale, f.pre_shift = sc.data_ptr(), sh.data_ptr()
+    if ln is not None:
+        st, ga, be = ln[0], _table16(ln[1]), _table16(ln[2])
+        assert st.dtype == torch.float32 and st.is_contiguous() and tuple(st.shape) == (M, 2)
+        keep += [st, ga, be]
+        f.ln_stats, f.ln_gamma, f.ln_beta = st.data_ptr(), ga.data_ptr(), be.data_ptr()
+    f.pre_act = int(pre_act)
+    if residual is not None:
+        if xs.dim() == 4:
+            residual = residual.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
+        res2 = residual.reshape(M, N).to(x.dtype).contiguous()
+        keep.append(res2)
+        f.residual, f.ldr = res2.data_ptr(), N
+    if bias_rows is not None:
+        br = bias_rows.reshape(B if xs.dim() == 4 else M, N).to(x.dtype).contiguous()
+        keep.append(br)
+        f.bias_rows = br.data_ptr()
+    f.geglu_out = int(bool(geglu))
+    ncols = N // 2 if geglu else N
+    y = torch.empty((M, ncols), dtype=x.dtype, device=x.device)
+    _lib_call("dgq_conv2d_wq_mfma16_fused", _lib.ptr(xs), _lib.DTYPE_CODE[x.dtype], *geom, int(upsample),
+              _lib.ptr(w_img), pw.bits, Kp, _lib.ptr(pw.alpha), _lib.ptr(pw.zp_true), _lib.ptr(pw.bias), N, int(geglu_rows),
+              _lib.ptr(y), _lib.DTYPE_CODE[y.dtype], ncols, _c.byref(f), _lib.stream())
+    del keep                                             # (the launch is enqueued on the tensors' stream: the allocator keeps their memory until it ran)
+    return result(y)
+
+
 # ------------------------------------------------------------------------------------------ attention side
 def fakequant_rows(x2d: torch.Tensor, T, D, mode, delta, zp, skip, bits, out=None):
     """x2d [rows][C] contiguous; see dgq_fakequant_rows."""

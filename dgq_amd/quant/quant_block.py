@@ -199,16 +199,24 @@ def _qparams(q: UniformAffineQuantizer, dev):
 
 class PreLN:
     """A tensor with an nn.LayerNorm pending.  QuantLayers on the integer path fold the norm into their quantise-on-load
-    pass (``forward_fused(x, ln=norm)``); anything else gets the materialised LayerNorm output (computed once)."""
+    pass (``forward_fused(x, ln=norm)``), and so do weight-only matrix-core layers under ``QuantLayer.weight_only_fused``, from the
+    row statistics cached here; anything else gets the materialised LayerNorm output (computed once)."""
 
     def __init__(self, x, norm):
-        self.x, self.norm, self._y = x, norm, None
+        self.x, self.norm, self._y, self._stats = x, norm, None, None
         self.shape, self.device, self.dtype, self.is_cuda = x.shape, x.device, x.dtype, x.is_cuda
 
     def materialise(self):
         if self._y is None:
             self._y = self.norm(self.x)
         return self._y
+
+    def row_stats(self):
+        """(mean, rstd) of the rows, for the layers that fold the norm on the weight-only matrix-core route (QuantLayer.takes_fused):
+        one launch for every consumer of the tensor — to_q, to_k and to_v of a self-attention share it"""
+        if self._stats is None:
+            self._stats = ops.layernorm_row_stats(self.x.reshape(-1, self.x.shape[-1]).contiguous(), float(self.norm.eps))
+        return self._stats
 
 
 def _fusable_ln(norm):
@@ -224,6 +232,8 @@ def _apply(layer, inp, **kw):
     """layer(inp) where inp may carry a pending LayerNorm"""
     if isinstance(inp, PreLN):
         if isinstance(layer, QuantLayer) and not layer.is_conv:
+            if layer.takes_fused(inp.x) and ops.layernorm_row_stats_ok(inp.x.shape[-1]) and not kw.get("pre_act") and kw.get("fq") is None:
+                kw = dict(kw, ln_stats=inp.row_stats())
             return layer.forward_fused(inp.x, ln=inp.norm, **kw)
         inp = inp.materialise()
     if kw:

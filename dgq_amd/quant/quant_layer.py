@@ -537,6 +537,11 @@ class QuantLayer(nn.Module):
     #: 16-bit matrix cores: not bit-identical to the exact route) — see takes_mfma16.  QuantModel.set_weight_only_mfma16
     #: sets it on every layer.
     weight_only_mfma16 = False
+    #: opt-in beside weight_only_mfma16, read at call time: the methods that fold a layer's element-wise neighbours on the integer path
+    #: (forward_prenorm, forward_residual, forward_fused, the *_tokens pair) fold them on the weight-only matrix-core route too
+    #: (dgq_conv2d_wq_mfma16_fused: norm, SiLU, GEGLU, residual and time-embedding rows in the one launch) instead of
+    #: running them as torch operators around dgq_conv2d_wq_mfma16 — see takes_fused.  QuantModel.set_weight_only_fused sets it.
+    weight_only_fused = False
 
     def __init__(self, layer: Union[nn.Conv2d, nn.Linear], wq_params: dict = {}, aq_params: dict = {},
                  disable_aq: bool = False, aq_mode: List[int] = [QMODE.QDIFF.value], quant_emb: bool = False) -> None:
@@ -824,6 +829,16 @@ class QuantLayer(nn.Module):
     def _weight_only_op(self):
         return ops.conv2d_wq_mfma16 if self.takes_mfma16() else ops.conv2d_wq
 
+    def takes_fused(self, x: torch.Tensor) -> bool:
+        """True when the folding methods run dgq_conv2d_wq_mfma16_fused on x: the switch is set, the call is on the packed weight-only
+        path and takes the matrix-core entry, and nothing has to see the un-fused pieces (no layer tap, no hooks, no calibration —
+        the conditions of forward_upsampled; autograd is excluded by the packed path itself)."""
+        return (self.weight_only_fused and LAYER_TAP is None and self.on_packed_weight_only_path(x) and self.takes_mfma16()
+                and not self.aqtizer.calibrating() and not self._forward_hooks and not self._forward_pre_hooks)
+
+    def _fused(self, x, **kw):
+        return ops.conv2d_wq_mfma16_fused(x, self.packed_weight(), *self._conv_geom(), geglu_rows=self.geglu_rows, **kw)
+
     def _weight_only_hip(self, x: torch.Tensor) -> bool:
         """what the weight-only state asks of x and of the layer before it leaves F.conv2d / F.linear for this library's kernels"""
         return WEIGHT_ONLY_HIP and x.dtype in ops.FLOAT_DTYPES and not (torch.is_grad_enabled() and x.requires_grad) and self._plain()
@@ -832,14 +847,30 @@ class QuantLayer(nn.Module):
         """True when forward(x) would run dgq_quant_act + dgq_gemm_wxa8 (weights and activations quantised, GPU)."""
         return self.use_wq and self.use_aq and not self.disable_aq and x.is_cuda and self._has_act_table()
 
-    def forward_fused(self, x: torch.Tensor, pre_act: int = 0, residual=None, fq=None, ln=None, geglu: bool = False) -> torch.Tensor:
+    def forward_fused(self, x: torch.Tensor, pre_act: int = 0, residual=None, fq=None, ln=None, geglu: bool = False, ln_stats=None) -> torch.Tensor:
         """``fq(self(act(x))) + residual`` with the elementwise pieces folded into the two kernels of the layer:
         pre_act 1 = SiLU(x), 2 = GEGLU (x[..., :K]·gelu(x[..., K:])) inside the quantise-on-load pass; ``fq`` (an
         attention-side quantizer, see ops.make_extra) and ``residual`` inside the GEMM epilogue.  Linear layers on the
         integer path only; anything else falls back to the unfused sequence of the same kernels/ops.  ``ln`` = an
         nn.LayerNorm module applied to x first, folded into the same load pass (per-row statistics in the kernel).
         ``geglu``: the layer is the GEGLU projection ff.net.0 and the result is value·gelu(gate), [..., N/2] — formed in the
-        GEMM epilogue when the packed rows are interleaved (``geglu_rows``)."""
+        GEMM epilogue when the packed rows are interleaved (``geglu_rows``).
+        On the weight-only matrix-core route with ``weight_only_fused`` (takes_fused) a Linear layer folds ln, SiLU, the residual and
+        the GEGLU into its one launch; ``ln_stats``: the rows' (mean, rstd) where the caller already has them
+        (ops.layernorm_row_stats; PreLN shares one launch among the consumers of a normalised tensor)."""
+        if (not self.is_conv and fq is None and pre_act in (0, 1) and self.takes_fused(x)
+                and (ln is None or (not pre_act and ops.layernorm_row_stats_ok(x.shape[-1])))):
+            lnp = None
+            if ln is not None:
+                st = ln_stats if ln_stats is not None else ops.layernorm_row_stats(x.reshape(-1, x.shape[-1]).contiguous(), float(ln.eps))
+                lnp = (st, ln.weight, ln.bias)
+            if geglu and not self.geglu_rows:                     # rows not interleaved: GEGLU as its own step
+                a, g = self._fused(x, ln=lnp, pre_act=pre_act).chunk(2, dim=-1)
+                y = a * F.gelu(g)
+                return y if residual is None else y + residual
+            if geglu and residual is not None:                    # (no caller asks for both: the kernel's GEGLU epilogue takes no residual)
+                return self._fused(x, ln=lnp, pre_act=pre_act, geglu=True) + residual
+            return self._fused(x, ln=lnp, pre_act=pre_act, residual=residual, geglu=geglu)
         if ln is not None and (self.is_conv or not self.on_integer_path(x) or x.dtype not in ops.FLOAT_DTYPES or pre_act
                                or x.shape[-1] % 4 or x.shape[-1] > 2048):
             x = ln(x)                                           # nn.LayerNorm module: unfused
@@ -869,12 +900,15 @@ class QuantLayer(nn.Module):
 
     def can_fuse_prenorm(self, x: torch.Tensor) -> bool:
         """True when this layer runs on the integer path, so a preceding GroupNorm(+SiLU) can be folded into its
-        quantise-on-load pass (dgq_groupnorm_scale_shift + dgq_quant_act prologue)."""
-        return self.is_conv and self.on_integer_path(x) and x.dtype in ops.FLOAT_DTYPES
+        quantise-on-load pass (dgq_groupnorm_scale_shift + dgq_quant_act prologue) — or on the weight-only matrix-core route with
+        ``weight_only_fused``, where it folds into that kernel's load (takes_fused)."""
+        return self.is_conv and x.dtype in ops.FLOAT_DTYPES and (self.on_integer_path(x) or self.takes_fused(x))
 
     def forward_prenorm(self, x: torch.Tensor, norm: nn.GroupNorm, silu: bool = True, residual=None, bias_rows=None, final: bool = False) -> torch.Tensor:
         """conv(act(GroupNorm(x))) [+ residual | + bias_rows[b, :, None, None]] without materialising the normalised tensor.
-        final: the result is the calling module's own result (a pending ops.OutputRedirect may place it)."""
+        final: the result is the calling module's own result (a pending ops.OutputRedirect may place it; not on the weight-only route)."""
+        if self.takes_fused(x):                                   # the weight-only matrix-core route
+            return self._fused(x, norm=(norm.num_groups, norm.eps, norm.weight, norm.bias, 1 if silu else 0), residual=residual, bias_rows=bias_rows)
         ab = self._binding()
         out, out2 = self._take_redirect(x) if (final and LAYER_TAP is None) else (None, None)
         return _tap(self, ops.quant_conv2d(x, ab, *self._conv_geom(),
@@ -887,10 +921,14 @@ class QuantLayer(nn.Module):
     #    GroupNorm in front of proj_in folds into its quantise-on-load pass, the residual behind proj_out into its GEMM epilogue,
     #    and proj_out leaves GroupNorm partials for the next resnet block — as the Conv2d projections of SD do.
     def can_fuse_tokens(self, x: torch.Tensor) -> bool:
-        return not self.is_conv and self.w.dim() == 2 and self.on_integer_path(x) and x.dtype in ops.FLOAT_DTYPES
+        return not self.is_conv and self.w.dim() == 2 and x.dtype in ops.FLOAT_DTYPES and (self.on_integer_path(x) or self.takes_fused(x))
 
     def forward_prenorm_tokens(self, x: torch.Tensor, norm: nn.GroupNorm) -> torch.Tensor:
         """Linear(GroupNorm(x).permute(0, 2, 3, 1).reshape(B, HW, C)) for x [B, C, H, W] -> [B, HW, N]."""
+        if self.takes_fused(x):                                   # the weight-only matrix-core route
+            y = self._fused(x, norm=(norm.num_groups, norm.eps, norm.weight, norm.bias, 0))
+            b, n, hh, ww = y.shape
+            return y.permute(0, 2, 3, 1).reshape(b, hh * ww, n)
         y = ops.quant_conv2d(x, self._binding(), 1, 1, 1, 0, norm=(norm.num_groups, norm.eps, norm.weight, norm.bias, 0), gn_out=False)
         b, n, hh, ww = y.shape
         return _tap(self, y.permute(0, 2, 3, 1).reshape(b, hh * ww, n), x=x, prologue=True)
@@ -900,6 +938,8 @@ class QuantLayer(nn.Module):
         final: the result is the calling module's own result (a pending ops.OutputRedirect may place it)."""
         b, n, hh, ww = residual.shape
         x = h.reshape(b, hh, ww, h.shape[-1]).permute(0, 3, 1, 2)
+        if self.takes_fused(h):                                   # the weight-only matrix-core route
+            return self._fused(x, residual=residual)
         o1, o2 = ops.take_redirect(b * hh * ww, n, x.dtype) if (final and LAYER_TAP is None) else (None, None)
         y = ops.quant_conv2d(x, self._binding(), 1, 1, 1, 0, residual=residual, out=o1, out2=o2)
         yt = y.permute(0, 2, 3, 1).reshape(b, hh * ww, n)
@@ -937,6 +977,8 @@ class QuantLayer(nn.Module):
             out, out2 = self._take_redirect(x) if (final and LAYER_TAP is None) else (None, None)
             return _tap(self, ops.quant_conv2d(x, self._binding(), *self._conv_geom(), residual=residual, out=out, out2=out2),
                         x=x, prologue=False, residual=residual)
+        if self.takes_fused(x):                                   # weight-only matrix-core route: the add in that kernel's epilogue
+            return self._fused(x, residual=residual)
         return self(x) + residual
 
     # -- state switches (quant_layer.py:663-686) -----------------------------------------------------------

@@ -112,6 +112,15 @@ class QuantModel(nn.Module):
             if isinstance(m, QuantLayer):
                 m.weight_only_mfma16 = bool(flag)
 
+    def set_weight_only_fused(self, flag: bool = True) -> None:
+        """Opt in to (or out of) folding norms, SiLU, GEGLU, residuals and time-embedding rows into the weight-only matrix-core layers
+        (QuantLayer.weight_only_fused, dgq_conv2d_wq_mfma16_fused) on every layer.  Off by default: x′ is rounded once more than the
+        torch operators round it.  It acts only beside ``set_weight_only_mfma16(True)``, in the weight-only state."""
+        self._drop_graphs()
+        for m in self.model.modules():
+            if isinstance(m, QuantLayer):
+                m.weight_only_fused = bool(flag)
+
     def set_attention_mfma16(self, flag: bool = True) -> None:
         """Opt in to (or out of) dgq_attention_mfma16 on every attention the quant blocks drive (their ``attention_mfma16`` flag): with
         activation quantisation off, attention on fp16 / bf16 tensors runs in one launch on the 16-bit matrix cores instead of the

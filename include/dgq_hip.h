@@ -48,7 +48,9 @@ extern "C" {
  *        dgq_quant_act_block / dgq_dequant_act_block / dgq_gemm_blockq with dgq_act_block_out_t and dgq_gemm_block_t; dgq_conv2d_wq_mfma16 (the weight-only
  *        state on the 16-bit matrix cores); dgq_attention_mfma16 (un-quantised attention of the 16-bit states on the same cores);
  *        dgq_attention_mfma16_f32 (the same for fp32 tensors, every operand a two-term bf16 split); the real-time MXFP6 mode,
- *        dgq_quant_act_mx6 / dgq_dequant_act_mx6 / dgq_pack_w_mx6 / dgq_gemm_mx6 with dgq_act_mx6_out_t and dgq_gemm_mx6_t */
+ *        dgq_quant_act_mx6 / dgq_dequant_act_mx6 / dgq_pack_w_mx6 / dgq_gemm_mx6 with dgq_act_mx6_out_t and dgq_gemm_mx6_t;
+ *        dgq_conv2d_wq_mfma16_fused with its dgq_wq16_fuse_t — norms, SiLU, GEGLU and the residual folded into the weight-only
+ *        matrix-core layer — and dgq_layernorm_row_stats */
 #define DGQ_ABI_VERSION 123
 int dgq_version(void);
 const char* dgq_last_error(void);
@@ -249,6 +251,41 @@ int dgq_conv2d_wq(const void* x, int x_dtype, int B, int H, int W, int C, int kh
 int dgq_conv2d_wq_mfma16(const void* x, int x_dtype, int B, int H, int W, int C, int kh, int kw, int stride, int pad, int upsample,
                          const uint8_t* w_packed, int w_bits, int Kp, const float* delta, const float* zp, const float* bias, int N,
                          int geglu_rows, void* y, int y_dtype, int ldy, void* stream);
+
+/* dgq_conv2d_wq_mfma16_fused: dgq_conv2d_wq_mfma16 with the layer's element-wise neighbours folded into its load and its epilogue
+ * (csrc/gemm_wonly16.hip).  Every pointer of `f` may be NULL; with f NULL or every field empty the call IS dgq_conv2d_wq_mfma16 (the
+ * same kernel, the same bits).
+ *   x′[m,k] = act(norm(x[m,k])) in fp32, in the order and rounding of the quantisers' folded prologue; 0 exactly for a tap outside the
+ *             image and for k >= K (padding comes after the norm and the activation);
+ *     norm: pre_scale / pre_shift [B][C] fp32 (GroupNorm folded: x·scale[b][c] + shift[b][c], b the image of the row's pixel, the
+ *           tables of dgq_groupnorm_scale_shift; allowed beside upsample),
+ *        or ln_stats [M][2] fp32 (mean, rstd) of dgq_layernorm_row_stats with ln_gamma / ln_beta [C] fp32 (LayerNorm folded:
+ *           (x − mean)·rstd·γ[c] + β[c]; kh = kw = 1, stride 1, no padding), or none;   pre_act: 0 none, 1 SiLU;
+ *   x̃ = x′ rounded once to the operand type (bf16 / f16 x) or its two-term bf16 split (fp32 x);  acc = Σ_k x̃·(q − zp), the same K loop;
+ *   t = delta[n]·acc + bias[n] [+ bias_rows[b(m)][n]];   y = round_to_y(t [+ residual[m][n]])  — all in fp32, ONE rounding;
+ *   geglu_out = 1 (needs geglu_rows, an even N, no residual): y[m][i] = round_to_y(t[m][2i]·gelu(t[m][2i + 1])), y is [M][ldy >= N/2].
+ * residual [M][ldr >= N] and bias_rows [B][N] hold y's dtype and are in the OUTPUT's column order: with geglu_rows = 1 packed row n reads
+ * them at the column it stands for (n/2, or n/2 + N/2 for odd n) — under geglu_out too, where bias_rows [B][N] holds the value columns
+ * first and the gate columns second.  The prologue's tables must be 16-byte aligned.  Refused: GroupNorm
+ * and LayerNorm fields both set, a LayerNorm on a k x k window, ln_stats without gamma and beta, geglu_out with a residual, ldr < N. */
+typedef struct {
+    const float* pre_scale; const float* pre_shift;
+    const float* ln_stats; const float* ln_gamma; const float* ln_beta;
+    int pre_act;
+    const void* residual; int ldr;
+    const void* bias_rows;
+    int geglu_out;
+} dgq_wq16_fuse_t;
+int dgq_conv2d_wq_mfma16_fused(const void* x, int x_dtype, int B, int H, int W, int C, int kh, int kw, int stride, int pad, int upsample,
+                               const uint8_t* w_packed, int w_bits, int Kp, const float* delta, const float* zp, const float* bias, int N,
+                               int geglu_rows, void* y, int y_dtype, int ldy, const dgq_wq16_fuse_t* f, void* stream);
+
+/* dgq_layernorm_row_stats: out[r] = (mean, rstd = 1/sqrt(var + eps)) of row r of x [rows][C] (biased variance, as nn.LayerNorm): one wave
+ * per row, the row read once, mean first, then Σ(x − mean)²; the sums and the final division, square root and reciprocal are carried in
+ * fp64 and rounded to fp32 once, so both values are the float64 statistics to within 2^-24 relative (the quantisers' folded LayerNorm
+ * evaluates the same two passes in fp32: its statistics agree to a few 2^-24, not bit for bit).  C % 4 == 0 and C <= 2048, x 16-byte
+ * aligned; anything else is refused. */
+int dgq_layernorm_row_stats(const void* x, int x_dtype, int rows, int C, float eps, float* out, void* stream);
 
 /* ---- the hot kernel: W4A8 / W8A8 MFMA GEMM with fused dequantisation ------------------------------
  * Replaces F.linear / `w.view(N,-1) @ unfolded` / F.conv2d on fake-quantised operands
