@@ -12,13 +12,13 @@
 // l >> 5 of the 64-deep step — 32 consecutive k as the 192-bit little-endian string of their 6-bit codes in the first six registers
 // (element j at bits 6j .. 6j + 5), and its scale in byte 0 of the scale register.
 //
-// The gather, tile and wave layout are gemm_blockq.hip's: 64 x 64 per workgroup, 8 waves (2 x 2 x 2, the two K waves meet in the
+// The gather, tile and wave layout are the block family's (gemm_gather.h, gemm_block.h; shared with gemm_blockq.hip): 64 x 64 per workgroup, 8 waves (2 x 2 x 2, the two K waves meet in the
 // epilogue's LDS transposition, k = 0 first), K tiles of 8 chunks, thread (row = tid & 63, chunk = tid >> 6) stages the 24 code bytes, the
 // scale byte and the weight piece of its (row, chunk); one MFMA covers the chunk pair (2i, 2i + 1), one chunk per lane half.  Chunk c =
 // tap·(C/32) + cb of output row m reads pixel (ho·stride − pad + dh, wo·stride − pad + dw) (>> ups); a tap outside the image (and the K
 // padding) stages zero codes under the scale 2^0 and contributes exactly 0.  The LDS images keep 32 bytes per (row, chunk) — a lane
 // reads 16 + 8 of them, as gemm_blockq.hip's fragment reads are spaced; the HBM images stay at 24.  No K split, no atomics.
-#include "gemm_tile.h"
+#include "gemm_block.h"
 
 DGQ_DIAG_BUFFER(mx6)
 
@@ -26,86 +26,44 @@ typedef int v8i __attribute__((ext_vector_type(8)));
 
 namespace {
 
-struct Mx6Geom {
-    const uint8_t* scale; int lds;
-    int B, H, W, Hs, Ws, C, cpb, kh, kw, stride, pad, ups, Ho, Wo;
-    int nch;                              // real chunks: kh·kw·C/32
-    int nchp;                             // chunks of the weight image: Kp / 32
-    int plain;                            // 1x1, stride 1, pad 0, no ups: pixel = row
-};
+struct Mx6Operand { const uint8_t* scale; int lds; };         // E8M0 byte per (pixel, block)
 
-constexpr int MX_BM = 64, MX_BN = 64, MX_NT = 512, MX_NW = 8;
-constexpr int MX_CH = 8;                                 // chunks per K tile = one staged chunk per wave
-constexpr int MX_A = MX_CH * MX_BM * 32, MX_W = MX_CH * MX_BN * 32;      // [chunk][row][32 B], 24 used
-constexpr int MX_SC = MX_CH * MX_BM;                                     // [chunk][row] scale bytes
-constexpr int MX_EP = MX_NW * 32 * (32 + 4) * 4;             // gemm_store_tile's transposition scratch (over the idle operand images)
-constexpr int MX_RING = MX_A + MX_W + MX_SC > MX_EP ? MX_A + MX_W + MX_SC : MX_EP;
+constexpr int MX_A = BLK_CH * BLK_BM * 32, MX_W = BLK_CH * BLK_BN * 32;  // [chunk][row][32 B], 24 used
+constexpr int MX_SC = BLK_CH * BLK_BM;                                   // [chunk][row] scale bytes
+constexpr int MX_RING = block_ring(MX_A + MX_W + MX_SC);
 
 template <typename TOut>
-__global__ __launch_bounds__(MX_NT) void gemm_mx6_kernel(GemmParams p, Mx6Geom q) {
-    static_assert(MX_CH == MX_NW, "one staged chunk per wave");
-    __shared__ __attribute__((aligned(16))) uint8_t smem[MX_RING + (3 * MX_BM + 4 * MX_BN) * 4];
+__global__ __launch_bounds__(BLK_NT) void gemm_mx6_kernel(GemmParams p, BlockGather q, Mx6Operand o) {
+    __shared__ __attribute__((aligned(16))) uint8_t smem[MX_RING + BLK_VEC];
     DGQ_DIAG_DECL
     DGQ_STAMP(0); DGQ_STAMP_REAL(1); DGQ_STAMP_WHERE(2);
     uint8_t* a_lds = smem;
     uint8_t* w_lds = smem + MX_A;
     uint8_t* sc_lds = smem + MX_A + MX_W;
-    float* vtab = reinterpret_cast<float*>(smem + MX_RING);   // [3][BM]: R0 R1 R2 | [4][BN]: alpha zw gamma vn
-    float* vcol = vtab + 3 * MX_BM;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wave_k = wid >> 2, wave_m = (wid >> 1) & 1, wave_n = wid & 1;
-    const int sch = wid;                                    // the chunk of a K tile this wave stages
-    const int m0 = blockIdx.y * MX_BM, n0 = blockIdx.x * MX_BN;
-    const int lr = lane & 31, hh = lane >> 5;
+    float* vtab = reinterpret_cast<float*>(smem + MX_RING);
+    const BlockRoles r = block_roles();
 
     // ---- the staged (row, chunk) of this thread: output position of the row, weight row of the column
-    const int srow = lane;                                  // = tid & 63
-    const int m = min(m0 + srow, p.M - 1);
-    int64_t pix0;                                           // first pixel of the row's image (plain: the row's own pixel)
-    int hbase = 0, wbase = 0;
-    if (q.plain) {
-        pix0 = m;
-    } else {
-        const int L = q.Ho * q.Wo;
-        const int b = m / L, l = m - b * L;
-        const int ho = l / q.Wo, wo = l - ho * q.Wo;
-        hbase = ho * q.stride - q.pad; wbase = wo * q.stride - q.pad;
-        pix0 = (int64_t)b * q.Hs * q.Ws;
-    }
-    const int n = min(n0 + srow, p.N - 1);
+    const BlockRow row = block_row(q, min(r.m0 + r.srow, p.M - 1));
+    const int n = min(r.n0 + r.srow, p.N - 1);
     const uint8_t* wrow = p.wpacked + (int64_t)n * q.nchp * 24;
     const int64_t apitch = (int64_t)q.cpb * 24;             // code bytes per pixel
 
     // ---- epilogue vectors: no row terms (R = 0), the column constants with zw = 0
-    if (tid < MX_BM) {
-        vtab[tid] = 1.0f; vtab[MX_BM + tid] = 0.0f; vtab[2 * MX_BM + tid] = 0.0f;
-        vcol[tid] = p.alpha[n]; vcol[MX_BN + tid] = 0.0f; vcol[2 * MX_BN + tid] = p.gamma[n]; vcol[3 * MX_BN + tid] = 0.0f;
-    }
+    if (r.tid < BLK_BM) block_vectors(vtab, vtab + 3 * BLK_BM, r.tid, p, n, 0.0f, 0.0f);
 
     // ---- staging registers of one K tile
     uint2 ra0, ra1, ra2, rw0, rw1, rw2;
     uint32_t rsc;
     auto load_tile = [&](int kt) {
-        const int cc = kt * MX_CH + sch;                    // wave-uniform chunk
+        const int cc = kt * BLK_CH + r.sch;                 // wave-uniform chunk
         ra0 = ra1 = ra2 = rw0 = rw1 = rw2 = make_uint2(0u, 0u);
         rsc = 127u;                                         // zero codes under 2^0: exactly 0
-        bool in = cc < q.nch;
-        int64_t pix = pix0;
-        int cb = cc;
-        if (!q.plain) {
-            const int tap = cc / q.cpb;
-            cb = cc - tap * q.cpb;
-            const int dh = tap / q.kw, dw = tap - dh * q.kw;
-            const int hi = hbase + dh, wi = wbase + dw;
-            in = in && (unsigned)hi < (unsigned)q.H && (unsigned)wi < (unsigned)q.W;
-            pix = pix0 + (int64_t)(hi >> q.ups) * q.Ws + (wi >> q.ups);
-        }
-        if (in) {
-            const uint2* src = reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(p.codes) + pix * apitch + cb * 24);
+        const BlockChunk x = block_chunk(q, row, cc);
+        if (x.in) {
+            const uint2* src = reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(p.codes) + x.pix * apitch + x.cb * 24);
             ra0 = src[0]; ra1 = src[1]; ra2 = src[2];
-            rsc = q.scale[pix * q.lds + cb];
+            rsc = o.scale[x.pix * o.lds + x.cb];
         }
         if (cc < q.nchp) {                                  // the weight image ends at Kp (a multiple of 4 chunks, not of 8)
             const uint2* src = reinterpret_cast<const uint2*>(wrow + cc * 24);
@@ -113,54 +71,45 @@ __global__ __launch_bounds__(MX_NT) void gemm_mx6_kernel(GemmParams p, Mx6Geom q
         }
     };
     auto store_tile = [&]() {
-        uint2* da = reinterpret_cast<uint2*>(a_lds + (sch * MX_BM + srow) * 32);
+        uint2* da = reinterpret_cast<uint2*>(a_lds + (r.sch * BLK_BM + r.srow) * 32);
         da[0] = ra0; da[1] = ra1; da[2] = ra2;
-        uint2* dw = reinterpret_cast<uint2*>(w_lds + (sch * MX_BN + srow) * 32);
+        uint2* dw = reinterpret_cast<uint2*>(w_lds + (r.sch * BLK_BN + r.srow) * 32);
         dw[0] = rw0; dw[1] = rw1; dw[2] = rw2;
-        sc_lds[sch * MX_BM + srow] = (uint8_t)rsc;
+        sc_lds[r.sch * BLK_BM + r.srow] = (uint8_t)rsc;
     };
 
     v16f accf[1][1];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) accf[0][0][r] = 0.0f;
-    const int arow = wave_m * 32 + lr, wcol = wave_n * 32 + lr;
-    const int nkt = (q.nch + MX_CH - 1) / MX_CH;
+    for (int i = 0; i < 16; ++i) accf[0][0][i] = 0.0f;
+    const int nkt = (q.nch + BLK_CH - 1) / BLK_CH;
     load_tile(0);
     for (int kt = 0; kt < nkt; ++kt) {
         store_tile();
         __syncthreads();
         if (kt + 1 < nkt) load_tile(kt + 1);
 #pragma unroll
-        for (int ii = 0; ii < MX_CH / 4; ++ii) {
-            const int pr = 2 * ii + wave_k;                 // this K wave's chunk pairs of the tile
-            if (kt * MX_CH + 2 * pr >= q.nch) break;        // (wave-uniform: both chunks of the pair are K padding)
-            const int ci = 2 * pr + hh;                     // the lane half's chunk = its K block of the 64-deep step
-            const uint8_t* ap = a_lds + (ci * MX_BM + arow) * 32;
-            const uint8_t* bp = w_lds + (ci * MX_BN + wcol) * 32;
+        for (int ii = 0; ii < BLK_CH / 4; ++ii) {
+            const int pr = 2 * ii + r.wave_k;               // this K wave's chunk pairs of the tile
+            if (kt * BLK_CH + 2 * pr >= q.nch) break;       // (wave-uniform: both chunks of the pair are K padding)
+            const int ci = 2 * pr + r.hh;                   // the lane half's chunk = its K block of the 64-deep step
+            const uint8_t* ap = a_lds + (ci * BLK_BM + r.arow) * 32;
+            const uint8_t* bp = w_lds + (ci * BLK_BN + r.wcol) * 32;
             const uint4 a4 = *reinterpret_cast<const uint4*>(ap);
             const uint2 a2 = *reinterpret_cast<const uint2*>(ap + 16);
             const uint4 b4 = *reinterpret_cast<const uint4*>(bp);
             const uint2 b2 = *reinterpret_cast<const uint2*>(bp + 16);
-            const int sa = sc_lds[ci * MX_BM + arow];
+            const int sa = sc_lds[ci * BLK_BM + r.arow];
             const v8i af = {(int)a4.x, (int)a4.y, (int)a4.z, (int)a4.w, (int)a2.x, (int)a2.y, 0, 0};
             const v8i bf = {(int)b4.x, (int)b4.y, (int)b4.z, (int)b4.w, (int)b2.x, (int)b2.y, 0, 0};
             accf[0][0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(af, bf, accf[0][0], 2, 2, 0, sa, 0, 128);
         }
         __syncthreads();
     }
-    DGQ_STAMP(6);
-    // (the barrier that ends the loop — or, with no K tile at all, none is needed: nothing was staged — has retired every read of the
-    // operand images; vtab / vcol were written before the loop's first barrier)
-    if (nkt == 0) __syncthreads();
-    v16i acc0[1][1];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc0[0][0][r] = 0;
-    gemm_store_tile<false, TOut, MX_BM, MX_BN, 2, 2, 2, MX_RING, 1, 1>(p, 0, smem, vtab, vcol, wid, lane, wave_m, wave_n, wave_k, m0, n0, acc0, accf DGQ_DIAG_ARG);
-    DGQ_STAMP(9);
-    DGQ_DIAG_DRAIN();
-    DGQ_STAMP(10); DGQ_STAMP_REAL(11);
-    DGQ_DIAG_FLUSH(mx6, MX_NW, wid, lane);
+    block_store<TOut, MX_RING>(p, smem, r, nkt, accf DGQ_DIAG_ARG);
+    DGQ_DIAG_FLUSH(mx6, BLK_NW, r.wid, r.lane);
 }
+
+struct Mx6Kernel { template <typename TOut> static constexpr auto fn = gemm_mx6_kernel<TOut>; };
 
 // E2M3 code of h = (q − z)/2 for an integer d = q − z, |d| <= 15: every such h is a grid value (0.5 is the subnormal 4/8; 1 .. 7.5 in
 // steps of 0.5 have at most 3 mantissa bits), so the code is read off the float's exponent and top mantissa bits, no rounding
@@ -198,12 +147,6 @@ __global__ void pack_w_mx6_kernel(const uint8_t* __restrict__ codes, const float
     }
 }
 
-template <typename TOut>
-void launch_mx6_t(const GemmParams& p, const Mx6Geom& q, hipStream_t st) {
-    const dim3 grid((p.N + MX_BN - 1) / MX_BN, (p.M + MX_BM - 1) / MX_BM), block(MX_NT);
-    hipLaunchKernelGGL((gemm_mx6_kernel<TOut>), grid, block, 0, st, p, q);
-}
-
 }  // namespace
 
 extern "C" int dgq_pack_w_mx6(const uint8_t* codes, const float* zw, int N, int C, int taps, int Kp, uint8_t* packed, void* stream) {
@@ -219,58 +162,14 @@ extern "C" int dgq_pack_w_mx6(const uint8_t* codes, const float* zw, int N, int 
 }
 
 extern "C" int dgq_gemm_mx6(const dgq_gemm_args_t* g, const dgq_gemm_mx6_t* mx, void* stream) {
-    DGQ_CHECK_ARG(g && mx, "dgq_gemm_mx6: null pointer");
-    const dgq_gemm_args_t& a = *g;
+    const char* who = "dgq_gemm_mx6";
+    DGQ_CHECK_ARG(g && mx && mx->scale, "dgq_gemm_mx6: null pointer");
     const dgq_gemm_mx6_t& k = *mx;
-    DGQ_CHECK_ARG(a.codes && a.wpacked && a.alpha && a.gamma && a.y && k.scale, "dgq_gemm_mx6: null pointer");
-    DGQ_CHECK_ARG(a.M > 0 && a.N > 0 && a.Kp > 0 && a.Kp % DGQ_KTILE == 0, "dgq_gemm_mx6: bad shape M=%d N=%d Kp=%d", a.M, a.N, a.Kp);
-    DGQ_CHECK_ARG(k.B > 0 && k.H > 0 && k.W > 0 && k.C > 0 && k.C % DGQ_KCHUNK == 0 && k.kh > 0 && k.kw > 0 && k.stride > 0 && k.pad >= 0,
-                  "dgq_gemm_mx6: bad geometry (C %% 32 == 0)");
-    const int ups = k.ups ? 1 : 0;
-    DGQ_CHECK_ARG(!ups || (k.H % 2 == 0 && k.W % 2 == 0), "dgq_gemm_mx6: ups needs even H, W");
-    const int Ho = (k.H + 2 * k.pad - k.kh) / k.stride + 1, Wo = (k.W + 2 * k.pad - k.kw) / k.stride + 1;
-    DGQ_CHECK_ARG(Ho > 0 && Wo > 0 && (int64_t)k.B * Ho * Wo == a.M, "dgq_gemm_mx6: M=%d is not B*Ho*Wo", a.M);
-    const int64_t K = (int64_t)k.kh * k.kw * k.C;
-    DGQ_CHECK_ARG(K <= a.Kp, "dgq_gemm_mx6: Kp=%d < kh*kw*C=%lld", a.Kp, (long long)K);
-    DGQ_CHECK_ARG(k.lds >= k.C / DGQ_KCHUNK, "dgq_gemm_mx6: scale pitch %d < %d blocks", k.lds, k.C / DGQ_KCHUNK);
-    DGQ_CHECK_ARG((int64_t)k.B * k.H * k.W * k.C < (1LL << 40), "dgq_gemm_mx6: input too large");
-    DGQ_CHECK_ARG((reinterpret_cast<uintptr_t>(a.codes) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.wpacked) & 15) == 0,
-                  "dgq_gemm_mx6: codes / wpacked must be 16-byte aligned");
-    const int out_cols = a.extra && a.extra->geglu ? a.N / 2 : a.N;
-    DGQ_CHECK_ARG(a.ldy >= out_cols, "dgq_gemm_mx6: ldy < output columns");
-    GemmParams p = {};
-    p.codes = a.codes; p.rowsum = nullptr; p.rowsum_parts = 1; p.M = a.M; p.Kp = a.Kp; p.N = a.N;
-    p.wpacked = reinterpret_cast<const uint8_t*>(a.wpacked);
-    p.L = 1; p.offset = 0.0f; p.alpha = a.alpha; p.zw = nullptr; p.gamma = a.gamma; p.y = a.y; p.ldy = a.ldy;
-    p.splits = 1; p.tiles_per_split = a.Kp / BK;
-    p.ex.res_div = 1; p.ex.fq_T = 1; p.ex.fq_D = 1; p.ex.fq_qmax = 255.0f;
-    if (a.extra) {
-        const dgq_gemm_extra_t& e = *a.extra;
-        DGQ_CHECK_ARG(!e.conv && !e.act, "dgq_gemm_mx6: no implicit-conv / quantise-on-load descriptor (the gather is this entry's own)");
-        DGQ_CHECK_ARG(e.fq_mode >= 0 && e.fq_mode <= 3, "dgq_gemm_mx6: bad fq_mode");
-        DGQ_CHECK_ARG(e.fq_mode == 0 || (e.fq_delta && e.fq_zp && e.fq_T > 0 && e.fq_D > 0), "dgq_gemm_mx6: fused quantizer needs tables");
-        DGQ_CHECK_ARG(!e.residual || (e.ldr >= a.N && e.res_div >= 1 && e.res_dtype >= DGQ_F32 && e.res_dtype <= DGQ_BF16),
-                      "dgq_gemm_mx6: bad residual descriptor (ldr < N, res_div < 1 or unknown dtype)");
-        DGQ_CHECK_ARG(!e.geglu || (a.N % 4 == 0 && !e.residual && e.fq_mode == 0), "dgq_gemm_mx6: the GEGLU epilogue needs N %% 4 == 0 and no other extra");
-        DGQ_CHECK_ARG(!e.y2 || (e.ldy2 >= a.N && !e.geglu), "dgq_gemm_mx6: y2 needs ldy2 >= N and no GEGLU epilogue");
-        DGQ_CHECK_ARG(!e.gn_partial || (a.M % 16 == 0 && a.N % 4 == 0 && !e.geglu && e.fq_mode == 0 && (reinterpret_cast<uintptr_t>(e.gn_partial) & 15) == 0),
-                      "dgq_gemm_mx6: GroupNorm partials need M %% 16 == 0, N %% 4 == 0, a 16-byte aligned buffer and no GEGLU / fused quantizer");
-        p.ex = e;
-        p.ex.conv = nullptr; p.ex.flush_coef = nullptr; p.ex.wfrag = nullptr; p.ex.act = nullptr;
-        if (!e.residual) p.ex.res_div = 1;
-    }
-    Mx6Geom q;
-    q.scale = k.scale; q.lds = k.lds; q.nchp = a.Kp / DGQ_KCHUNK;
-    q.B = k.B; q.H = k.H; q.W = k.W; q.Hs = k.H >> ups; q.Ws = k.W >> ups; q.C = k.C; q.cpb = k.C / DGQ_KCHUNK;
-    q.kh = k.kh; q.kw = k.kw; q.stride = k.stride; q.pad = k.pad; q.ups = ups; q.Ho = Ho; q.Wo = Wo;
-    q.nch = (int)(K / DGQ_KCHUNK);
-    q.plain = (k.kh == 1 && k.kw == 1 && k.stride == 1 && k.pad == 0 && !ups) ? 1 : 0;
-    hipStream_t st = (hipStream_t)stream;
-    switch (a.y_dtype) {
-        case DGQ_F32: launch_mx6_t<float>(p, q, st); break;
-        case DGQ_F16: launch_mx6_t<__half>(p, q, st); break;
-        case DGQ_BF16: launch_mx6_t<__hip_bfloat16>(p, q, st); break;
-        default: dgq_set_error("dgq_gemm_mx6: unknown y dtype %d", a.y_dtype); return DGQ_EINVAL;
-    }
-    return dgq_launch_status("dgq_gemm_mx6");
+    GemmParams p;
+    BlockGather q;
+    const int rc = block_gemm_setup(who, *g, k.B, k.H, k.W, k.C, k.kh, k.kw, k.stride, k.pad, k.ups, false, p, q);
+    if (rc != DGQ_OK) return rc;
+    DGQ_CHECK_ARG(k.lds >= q.cpb, "dgq_gemm_mx6: scale pitch %d < %d blocks", k.lds, q.cpb);
+    const Mx6Operand o = {k.scale, k.lds};
+    return block_gemm_launch<Mx6Kernel>(who, p, q, o, g->y_dtype, (hipStream_t)stream);
 }

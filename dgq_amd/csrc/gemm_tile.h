@@ -46,6 +46,21 @@ struct GemmParams {
     dgq_gemm_act_t act;   // quantise-on-load inside the panel kernel (act.x != nullptr; ex.act), see include/dgq_hip.h
 };
 
+// The ONE host-side check of what the store epilogue reads of a dgq_gemm_extra_t (fused quantizer, residual, GEGLU, y2, GroupNorm
+// partials) for an M x N problem; `who` names the entry in the message.  The operand descriptors (wfrag / act / flush_coef / conv)
+// are their entries' own.
+static inline int gemm_check_extra(const char* who, int M, int N, const dgq_gemm_extra_t& e) {
+    DGQ_CHECK_ARG(e.fq_mode >= 0 && e.fq_mode <= 3, "%s: bad fq_mode", who);
+    DGQ_CHECK_ARG(e.fq_mode == 0 || (e.fq_delta && e.fq_zp && e.fq_T > 0 && e.fq_D > 0), "%s: fused quantizer needs tables", who);
+    DGQ_CHECK_ARG(!e.residual || (e.ldr >= N && e.res_div >= 1 && e.res_dtype >= DGQ_F32 && e.res_dtype <= DGQ_BF16),
+                  "%s: bad residual descriptor (ldr < N, res_div < 1 or unknown dtype)", who);
+    DGQ_CHECK_ARG(!e.geglu || (N % 4 == 0 && !e.residual && e.fq_mode == 0), "%s: the GEGLU epilogue needs N %% 4 == 0 and no other extra", who);
+    DGQ_CHECK_ARG(!e.y2 || (e.ldy2 >= N && !e.geglu), "%s: y2 (second copy of the output rows) needs ldy2 >= N and no GEGLU epilogue", who);
+    DGQ_CHECK_ARG(!e.gn_partial || (M % 16 == 0 && N % 4 == 0 && !e.geglu && e.fq_mode == 0 && (reinterpret_cast<uintptr_t>(e.gn_partial) & 15) == 0),
+                  "%s: GroupNorm partials need M %% 16 == 0, N %% 4 == 0, a 16-byte aligned buffer and no GEGLU / fused quantizer", who);
+    return DGQ_OK;
+}
+
 // Up to DGQ_GEMM_BATCH problems of one kernel instance (tile shape, weight bits, scale mode, output dtype; no K split) in
 // ONE launch: blockIdx.z = problem.  Grid x / y cover the widest problem; blocks outside a problem's tile grid exit.
 #define DGQ_GEMM_BATCH 8

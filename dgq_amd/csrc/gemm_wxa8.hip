@@ -863,12 +863,8 @@ static int fill_gemm(const dgq_gemm_args_t& a, GemmParams& p) {
     p.alpha = a.alpha; p.zw = a.zw; p.gamma = a.gamma; p.vn = a.vn; p.y = a.y; p.ldy = a.ldy;
     if (a.extra) {
         p.ex = *a.extra;
-        DGQ_CHECK_ARG(p.ex.fq_mode >= 0 && p.ex.fq_mode <= 3, "dgq_gemm_wxa8: bad fq_mode");
-        DGQ_CHECK_ARG(p.ex.fq_mode == 0 || (p.ex.fq_delta && p.ex.fq_zp && p.ex.fq_T > 0 && p.ex.fq_D > 0), "dgq_gemm_wxa8: fused quantizer needs tables");
-        DGQ_CHECK_ARG(!p.ex.residual || (p.ex.ldr >= a.N && p.ex.res_div >= 1 && p.ex.res_dtype >= DGQ_F32 && p.ex.res_dtype <= DGQ_BF16),
-                      "dgq_gemm_wxa8: bad residual descriptor (ldr < N, res_div < 1 or unknown dtype)");
-        DGQ_CHECK_ARG(!p.ex.geglu || (a.N % 4 == 0 && !p.ex.residual && p.ex.fq_mode == 0),
-                      "dgq_gemm_wxa8: the GEGLU epilogue needs N %% 4 == 0 and no other extra");
+        const int rc = gemm_check_extra("dgq_gemm_wxa8", a.M, a.N, p.ex);
+        if (rc != DGQ_OK) return rc;
         if (p.ex.wfrag) {
             DGQ_CHECK_ARG(a.w_bits == 4 && (reinterpret_cast<uintptr_t>(p.ex.wfrag) & 15) == 0, "dgq_gemm_wxa8: wfrag is the W4 layout-2 image, 16-byte aligned");
             p.wfrag = reinterpret_cast<const uint8_t*>(p.ex.wfrag);
@@ -897,10 +893,6 @@ static int fill_gemm(const dgq_gemm_args_t& a, GemmParams& p) {
                           "dgq_gemm_wxa8: bad implicit-conv descriptor (needs per_m with L = 1, W4, C %% 16 == 0, M = B*Ho*Wo, 16-byte aligned codes_in / fill)");
             p.cv = c;
         }
-        DGQ_CHECK_ARG(!p.ex.y2 || (p.ex.ldy2 >= a.N && !p.ex.geglu), "dgq_gemm_wxa8: y2 (second copy of the output rows) needs ldy2 >= N and no GEGLU epilogue");
-        DGQ_CHECK_ARG(!p.ex.gn_partial || (a.M % 16 == 0 && a.N % 4 == 0 && !p.ex.geglu && p.ex.fq_mode == 0 &&
-                                           (reinterpret_cast<uintptr_t>(p.ex.gn_partial) & 15) == 0),
-                      "dgq_gemm_wxa8: GroupNorm partials need M %% 16 == 0, N %% 4 == 0, a 16-byte aligned buffer and no GEGLU / fused quantizer");
     } else {
         p.ex.residual = nullptr; p.ex.ldr = 0; p.ex.res_div = 1; p.ex.res_dtype = DGQ_F32; p.ex.fq_mode = 0; p.ex.fq_delta = nullptr; p.ex.fq_zp = nullptr;
         p.ex.fq_T = 1; p.ex.fq_D = 1; p.ex.fq_skip = 0; p.ex.fq_qmax = 255.0f; p.ex.geglu = 0; p.ex.gn_partial = nullptr; p.ex.conv = nullptr; p.ex.flush_coef = nullptr; p.ex.wfrag = nullptr; p.ex.act = nullptr;

@@ -35,16 +35,7 @@ __global__ __launch_bounds__(256) void quant_block_kernel(BlockQuantProblem p) {
     int8_t* crow = p.codes + (int64_t)row * in.C;
     float2* trow = p.table + (int64_t)row * p.ldt;
     float rho = 0.0f;
-    // wave-uniform steps of 256 channels = 8 blocks; C % 32 == 0, so the 8 lanes of a block are all inside the row or all past it (a
-    // block past the end computes on a clamped address and stores nothing)
-    for (int base = 0; base < in.C; base += 256) {
-        const int c0 = base + lane * 4;
-        const bool inside = c0 < in.C;
-        const int c = min(c0, in.C - 4);
-        float v[4], g[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        load4<TIn>(s.xr + c, v);
-        if (in.pre_act == 2) load4<TIn>(s.xr + in.C + c, g);
-        dgq_prologue4(v, c, s.pre_sc, s.pre_sh, in.ln_gamma, in.ln_beta, s.ln_mu, s.ln_rstd, in.pre_act, g);
+    quant_block_walk<TIn>(in, s, lane, [&](const float (&v)[4], int c, bool inside, int base) {
         float mn = fminf(0.0f, fminf(fminf(v[0], v[1]), fminf(v[2], v[3])));       // MINMAX includes 0 in the range
         float mx = fmaxf(0.0f, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
 #pragma unroll
@@ -72,7 +63,7 @@ __global__ __launch_bounds__(256) void quant_block_kernel(BlockQuantProblem p) {
             const float t = __shfl(term, 8 * j, 64);
             if (base + 32 * j < in.C) rho += t;
         }
-    }
+    });
     for (int cb = (in.C >> 5) + lane; cb < p.ldt; cb += 64) trow[cb] = make_float2(0.0f, 0.0f);
     if (lane == 0) p.rho[row] = rho;
 }
@@ -85,15 +76,12 @@ extern "C" int dgq_quant_act_block(const dgq_quant_act_args_t* in, const dgq_act
     DGQ_CHECK_ARG(((uintptr_t)o.codes & 15) == 0 && ((uintptr_t)o.table & 7) == 0,
                   "dgq_quant_act_block: codes must be 16-byte aligned, the table 8-byte aligned");
     BlockQuantProblem p;
-    int Ho, Wo;
-    const int rc = dgq_check_quant_input(a, "dgq_quant_act_block", {DGQ_KCHUNK, false, true}, p.in, Ho, Wo);
+    dim3 grid, block(256);
+    const int rc = dgq_check_block_quant(a, "dgq_quant_act_block", o.ldt, p.in, grid);
     if (rc != DGQ_OK) return rc;
-    DGQ_CHECK_ARG(o.ldt >= a.C / DGQ_KCHUNK, "dgq_quant_act_block: table pitch %d < %d blocks", o.ldt, a.C / DGQ_KCHUNK);
-    DGQ_CHECK_ARG((int64_t)p.in.rows * a.C < (1LL << 40), "dgq_quant_act_block: too many rows");
     p.qmax = p.in.levels; p.offset = (float)(1 << (a.bits - 1));
     p.codes = o.codes; p.table = reinterpret_cast<float2*>(o.table); p.ldt = o.ldt; p.rho = o.rho;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((p.in.rows + 3) / 4), block(256);
     DGQ_QUANT_DTYPE_SWITCH(a.x_dtype, "dgq_quant_act_block", hipLaunchKernelGGL((quant_block_kernel<TIn>), grid, block, 0, st, p))
     return dgq_launch_status("dgq_quant_act_block");
 }
@@ -115,11 +103,11 @@ __global__ __launch_bounds__(256) void dequant_block_kernel(const int8_t* codes,
 
 extern "C" int dgq_dequant_act_block(const int8_t* codes, const float* table, int ldt, int64_t rows, int C, void* y, int y_dtype, void* stream) {
     DGQ_CHECK_ARG(codes && table && y, "dgq_dequant_act_block: null pointer");
-    DGQ_CHECK_ARG(rows > 0 && C > 0 && C % DGQ_KCHUNK == 0 && ldt >= C / DGQ_KCHUNK && rows * C < (1LL << 40),
-                  "dgq_dequant_act_block: bad shape rows=%lld C=%d ldt=%d", (long long)rows, C, ldt);
+    dim3 grid, block(256);
+    const int rc = dgq_check_block_dequant("dgq_dequant_act_block", rows, C, ldt, grid);
+    if (rc != DGQ_OK) return rc;
     DGQ_CHECK_ARG(((uintptr_t)codes & 3) == 0 && ((uintptr_t)table & 7) == 0, "dgq_dequant_act_block: codes 4-byte, table 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((rows * C / 4 + 255) / 256)), block(256);
     const float2* tb = reinterpret_cast<const float2*>(table);
     DGQ_QUANT_DTYPE_SWITCH(y_dtype, "dgq_dequant_act_block",
                            hipLaunchKernelGGL((dequant_block_kernel<TIn>), grid, block, 0, st, codes, tb, ldt, rows, C, reinterpret_cast<TIn*>(y)))

@@ -46,16 +46,7 @@ __global__ __launch_bounds__(256) void quant_mx6_kernel(Mx6QuantProblem p) {
     const QuantRowSource<TIn> s = quant_row_source<TIn>(in, row, lane);
     uint8_t* crow = p.codes + (int64_t)row * (in.C / 4 * 3);
     uint8_t* srow = p.scale + (int64_t)row * p.lds;
-    // wave-uniform steps of 256 channels = 8 blocks; C % 32 == 0, so the 8 lanes of a block are all inside the row or all past it (a
-    // block past the end computes on a clamped address and stores nothing)
-    for (int base = 0; base < in.C; base += 256) {
-        const int c0 = base + lane * 4;
-        const bool inside = c0 < in.C;
-        const int c = min(c0, in.C - 4);
-        float v[4], g[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        load4<TIn>(s.xr + c, v);
-        if (in.pre_act == 2) load4<TIn>(s.xr + in.C + c, g);
-        dgq_prologue4(v, c, s.pre_sc, s.pre_sh, in.ln_gamma, in.ln_beta, s.ln_mu, s.ln_rstd, in.pre_act, g);
+    quant_block_walk<TIn>(in, s, lane, [&](const float (&v)[4], int c, bool inside, int) {
         // max |x′| as an integer (the bits of a non-negative finite float order like the value)
         uint32_t am = max(max(__float_as_uint(v[0]) & 0x7FFFFFFFu, __float_as_uint(v[1]) & 0x7FFFFFFFu),
                           max(__float_as_uint(v[2]) & 0x7FFFFFFFu, __float_as_uint(v[3]) & 0x7FFFFFFFu));
@@ -70,7 +61,7 @@ __global__ __launch_bounds__(256) void quant_mx6_kernel(Mx6QuantProblem p) {
             if (t < 3) *reinterpret_cast<uint32_t*>(crow + (c >> 2) * 3 + t) = (piece >> (8 * t)) | (next << (24 - 8 * t));
             if ((lane & 7) == 0) srow[c >> 5] = (uint8_t)(E + 127);
         }
-    }
+    });
     for (int cb = (in.C >> 5) + lane; cb < p.lds; cb += 64) srow[cb] = 127;
 }
 
@@ -81,14 +72,11 @@ extern "C" int dgq_quant_act_mx6(const dgq_quant_act_args_t* in, const dgq_act_m
     DGQ_CHECK_ARG(o.codes && o.scale, "dgq_quant_act_mx6: null pointer");
     DGQ_CHECK_ARG(((uintptr_t)o.codes & 15) == 0, "dgq_quant_act_mx6: codes must be 16-byte aligned");
     Mx6QuantProblem p;
-    int Ho, Wo;
-    const int rc = dgq_check_quant_input(a, "dgq_quant_act_mx6", {DGQ_KCHUNK, false, true}, p.in, Ho, Wo);
+    dim3 grid, block(256);
+    const int rc = dgq_check_block_quant(a, "dgq_quant_act_mx6", o.lds, p.in, grid);
     if (rc != DGQ_OK) return rc;
-    DGQ_CHECK_ARG(o.lds >= a.C / DGQ_KCHUNK, "dgq_quant_act_mx6: scale pitch %d < %d blocks", o.lds, a.C / DGQ_KCHUNK);
-    DGQ_CHECK_ARG((int64_t)p.in.rows * a.C < (1LL << 40), "dgq_quant_act_mx6: too many rows");
     p.codes = o.codes; p.scale = o.scale; p.lds = o.lds;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((p.in.rows + 3) / 4), block(256);
     DGQ_QUANT_DTYPE_SWITCH(a.x_dtype, "dgq_quant_act_mx6", hipLaunchKernelGGL((quant_mx6_kernel<TIn>), grid, block, 0, st, p))
     return dgq_launch_status("dgq_quant_act_mx6");
 }
@@ -115,10 +103,10 @@ __global__ __launch_bounds__(256) void dequant_mx6_kernel(const uint8_t* codes, 
 
 extern "C" int dgq_dequant_act_mx6(const uint8_t* codes, const uint8_t* scale, int lds, int64_t rows, int C, void* y, int y_dtype, void* stream) {
     DGQ_CHECK_ARG(codes && scale && y, "dgq_dequant_act_mx6: null pointer");
-    DGQ_CHECK_ARG(rows > 0 && C > 0 && C % DGQ_KCHUNK == 0 && lds >= C / DGQ_KCHUNK && rows * C < (1LL << 40),
-                  "dgq_dequant_act_mx6: bad shape rows=%lld C=%d lds=%d", (long long)rows, C, lds);
+    dim3 grid, block(256);
+    const int rc = dgq_check_block_dequant("dgq_dequant_act_mx6", rows, C, lds, grid);
+    if (rc != DGQ_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((rows * C / 4 + 255) / 256)), block(256);
     DGQ_QUANT_DTYPE_SWITCH(y_dtype, "dgq_dequant_act_mx6",
                            hipLaunchKernelGGL((dequant_mx6_kernel<TIn>), grid, block, 0, st, codes, scale, lds, rows, C, reinterpret_cast<TIn*>(y)))
     return dgq_launch_status("dgq_dequant_act_mx6");

@@ -147,6 +147,42 @@ static inline int dgq_check_quant_input(const dgq_quant_act_args_t& a, const cha
         default: dgq_set_error("%s: unknown dtype %d", who, dtype); return DGQ_EINVAL;    \
     }
 
+// ---- the real-time BLOCK quantisers (quant_block.hip, quant_mx6.hip): one wave per input row, four rows per 256-thread block; a lane
+// holds 4 consecutive channels, 8 lanes one 32-channel block.
+// The row walk: wave-uniform steps of 256 channels = 8 blocks; C % 32 == 0, so the 8 lanes of a block are all inside the row or all
+// past it (a block past the end computes on a clamped address and must store nothing).  Per step body(v, c, inside, base) gets the
+// lane's four x′ behind the folded prologue, their first channel c (clamped), whether the lane's block is inside, and the step's base.
+template <typename TIn, typename Body>
+__device__ __forceinline__ void quant_block_walk(const QuantRowInput& in, const QuantRowSource<TIn>& s, int lane, Body&& body) {
+    for (int base = 0; base < in.C; base += 256) {
+        const int c0 = base + lane * 4;
+        const bool inside = c0 < in.C;
+        const int c = min(c0, in.C - 4);
+        float v[4], g[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        load4<TIn>(s.xr + c, v);
+        if (in.pre_act == 2) load4<TIn>(s.xr + in.C + c, g);
+        dgq_prologue4(v, c, s.pre_sc, s.pre_sh, in.ln_gamma, in.ln_beta, s.ln_mu, s.ln_rstd, in.pre_act, g);
+        body(v, c, inside, base);
+    }
+}
+// host side of the two entries: the input check, the pitch of the per-block output (>= C/32 entries per row) and the grid
+static inline int dgq_check_block_quant(const dgq_quant_act_args_t& a, const char* who, int pitch, QuantRowInput& in, dim3& grid) {
+    int Ho, Wo;
+    const int rc = dgq_check_quant_input(a, who, {DGQ_KCHUNK, false, true}, in, Ho, Wo);
+    if (rc != DGQ_OK) return rc;
+    DGQ_CHECK_ARG(pitch >= a.C / DGQ_KCHUNK, "%s: block pitch %d < %d blocks", who, pitch, a.C / DGQ_KCHUNK);
+    DGQ_CHECK_ARG((int64_t)in.rows * a.C < (1LL << 40), "%s: too many rows", who);
+    grid = dim3((in.rows + 3) / 4);
+    return DGQ_OK;
+}
+// ... and of the two dequant entries (four codes per thread): the shape check and the grid
+static inline int dgq_check_block_dequant(const char* who, int64_t rows, int C, int pitch, dim3& grid) {
+    DGQ_CHECK_ARG(rows > 0 && C > 0 && C % DGQ_KCHUNK == 0 && pitch >= C / DGQ_KCHUNK && rows * C < (1LL << 40),
+                  "%s: bad shape rows=%lld C=%d pitch=%d", who, (long long)rows, C, pitch);
+    grid = dim3((unsigned)((rows * C / 4 + 255) / 256));
+    return DGQ_OK;
+}
+
 // MINMAX of one row from its extrema (0 already included): dgq_amd/quant/quant_layer.py row_minmax.  fp64 for the range and its division, one
 // rounding to fp32; IEEE fp32 division for z (no reciprocal).
 __device__ __forceinline__ void minmax_params(float lo, float hi, float levels, float& delta, float& zp) {

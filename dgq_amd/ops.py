@@ -923,28 +923,64 @@ def gemm_wxa8(codes, rowsum, M, ab: ActBinding, out_dtype, out: Optional[torch.T
 BLOCK_LAUNCH_HOOK = None
 
 
+def _block_quant_launch(entry, x_cl, geom, bits, pre, ln, ups, pitch, outputs):
+    """One launch of a block quantiser entry on the layer INPUT x_cl: rows = the input's rows / pixels (the SOURCE pixels with ``ups``),
+    pitch = per-block entries of a row (default C/32).  outputs(rows, C, pitch, device) -> (the entry's output struct, its tensors);
+    returns the tensors."""
+    B, H, W, C = geom[:4]
+    sh = 1 if ups else 0
+    rows = B * (H >> sh) * (W >> sh)
+    a, keep = _quant_input(x_cl, geom, bits, pre, ln, ups)
+    o, res = outputs(rows, C, C // 32 if pitch is None else pitch, x_cl.device)
+
+    def issue(_keep=(keep, res)):
+        _lib_call(entry, _c.byref(a), _c.byref(o), _lib.stream())
+    issue()
+    if BLOCK_LAUNCH_HOOK is not None:
+        BLOCK_LAUNCH_HOOK(issue, "quant", (rows, C))
+    return res
+
+
+def _block_gemm_launch(entry, k, q, geom, ab, out_dtype, out, extra, ups, **own):
+    """One launch of a block GEMM entry on q = its quantiser's result (q[0]: the codes): the dgq_gemm_args_t of a block-mode layer —
+    ``own``: the fields the format adds — and the geometry of k, the format's struct carrying its own fields.  Returns y."""
+    B, H, W, C, kh, kw, stride, pad = geom
+    M = B * ((H + 2 * pad - kh) // stride + 1) * ((W + 2 * pad - kw) // stride + 1)
+    pw = ab.pw
+    if out is None:
+        out = torch.empty((M, pw.N // 2 if (extra is not None and extra.geglu) else pw.N), dtype=out_dtype, device=q[0].device)
+    g = _lib.GemmArgs()
+    g.codes, g.rowsum_parts = q[0].data_ptr(), 1
+    g.M, g.Kp, g.wpacked, g.N, g.per_m, g.L = M, ab.Kp, ab.wpacked.data_ptr(), pw.N, 0, 1
+    g.alpha, g.gamma = pw.alpha.data_ptr(), ab.gamma.data_ptr()
+    g.y, g.y_dtype, g.ldy = out.data_ptr(), _lib.DTYPE_CODE[out.dtype], out.stride(0)
+    for name, value in own.items():
+        setattr(g, name, value)
+    if extra is not None:
+        g.extra = _c.cast(_c.pointer(extra), _c.c_void_p)
+    k.B, k.H, k.W, k.C, k.kh, k.kw, k.stride, k.pad, k.ups = B, H, W, C, kh, kw, stride, pad, 1 if ups else 0
+
+    def issue(_keep=(q, out, extra, ab)):
+        _lib_call(entry, _c.byref(g), _c.byref(k), _lib.stream())
+    issue()
+    if BLOCK_LAUNCH_HOOK is not None:
+        BLOCK_LAUNCH_HOOK(issue, "gemm", (M, pw.N, pw.K))
+    return out
+
+
 def quant_act_block(x_cl: torch.Tensor, geom, bits, pre=None, ln=None, ups=False, ldt=None):
     """dgq_quant_act_block on the layer INPUT x_cl (channels-last storage, geom = (B, H, W, C, kh, kw, stride, pad) as for quant_act):
     one launch.  Returns (codes int8 [rows][C], table fp32 [rows][ldt][2] = {δ, β} per 32-channel block, ρ fp32 [rows]) with rows =
     the input's rows / pixels (the SOURCE pixels with ``ups``); ldt (default C/32) > C/32 adds zeroed entries (a Linear layer's K
     padding).  pre / ln / ups as in quant_act."""
-    B, H, W, C = geom[:4]
-    sh = 1 if ups else 0
-    rows = B * (H >> sh) * (W >> sh)
-    ldt = C // 32 if ldt is None else ldt
-    a, keep = _quant_input(x_cl, geom, bits, pre, ln, ups)
-    codes = torch.empty((rows, C), dtype=torch.int8, device=x_cl.device)
-    table = torch.empty((rows, ldt, 2), dtype=torch.float32, device=x_cl.device)
-    rho = torch.empty((rows,), dtype=torch.float32, device=x_cl.device)
-    o = _lib.ActBlockOut()
-    o.codes, o.table, o.ldt, o.rho = codes.data_ptr(), table.data_ptr(), ldt, rho.data_ptr()
-
-    def issue(_keep=(keep, codes, table, rho)):
-        _lib_call("dgq_quant_act_block", _c.byref(a), _c.byref(o), _lib.stream())
-    issue()
-    if BLOCK_LAUNCH_HOOK is not None:
-        BLOCK_LAUNCH_HOOK(issue, "quant", (rows, C))
-    return codes, table, rho
+    def outputs(rows, C, ldt, dev):
+        codes = torch.empty((rows, C), dtype=torch.int8, device=dev)
+        table = torch.empty((rows, ldt, 2), dtype=torch.float32, device=dev)
+        rho = torch.empty((rows,), dtype=torch.float32, device=dev)
+        o = _lib.ActBlockOut()
+        o.codes, o.table, o.ldt, o.rho = codes.data_ptr(), table.data_ptr(), ldt, rho.data_ptr()
+        return o, (codes, table, rho)
+    return _block_quant_launch("dgq_quant_act_block", x_cl, geom, bits, pre, ln, ups, ldt, outputs)
 
 
 def dequant_act_block(codes, table, out):
@@ -958,52 +994,24 @@ def dequant_act_block(codes, table, out):
 def gemm_blockq(q, geom, ab: "BlockActBinding", out_dtype, out=None, extra=None, ups=False):
     """One dgq_gemm_blockq launch on q = quant_act_block(...) of the layer input; geom = (B, H, W, C, kh, kw, stride, pad) of the layer
     (H, W: behind a folded upsample).  Returns y [M][N] (N/2 columns with the GEGLU epilogue)."""
-    codes, table, rho = q
-    B, H, W, C, kh, kw, stride, pad = geom
-    M = B * ((H + 2 * pad - kh) // stride + 1) * ((W + 2 * pad - kw) // stride + 1)
-    pw = ab.pw
-    if out is None:
-        out = torch.empty((M, pw.N // 2 if (extra is not None and extra.geglu) else pw.N), dtype=out_dtype, device=codes.device)
-    g = _lib.GemmArgs()
-    g.codes, g.rowsum, g.rowsum_parts = codes.data_ptr(), rho.data_ptr(), 1
-    g.M, g.Kp, g.wpacked, g.w_bits, g.N, g.per_m, g.L = M, ab.Kp, ab.wpacked.data_ptr(), pw.bits, pw.N, 0, 1
-    g.offset = ab.offset
-    g.alpha, g.zw, g.gamma = pw.alpha.data_ptr(), pw.zw.data_ptr(), ab.gamma.data_ptr()
-    g.y, g.y_dtype, g.ldy = out.data_ptr(), _lib.DTYPE_CODE[out.dtype], out.stride(0)
-    if extra is not None:
-        g.extra = _c.cast(_c.pointer(extra), _c.c_void_p)
+    _, table, rho = q
     k = _lib.GemmBlock()
     k.table, k.ldt, k.vc = table.data_ptr(), table.shape[1], ab.vc.data_ptr()
-    k.B, k.H, k.W, k.C, k.kh, k.kw, k.stride, k.pad, k.ups = B, H, W, C, kh, kw, stride, pad, 1 if ups else 0
-
-    def issue(_keep=(q, out, extra, ab)):
-        _lib_call("dgq_gemm_blockq", _c.byref(g), _c.byref(k), _lib.stream())
-    issue()
-    if BLOCK_LAUNCH_HOOK is not None:
-        BLOCK_LAUNCH_HOOK(issue, "gemm", (M, pw.N, pw.K))
-    return out
+    return _block_gemm_launch("dgq_gemm_blockq", k, q, geom, ab, out_dtype, out, extra, ups, w_bits=ab.pw.bits, rowsum=rho.data_ptr(),
+                              offset=ab.offset, zw=ab.pw.zw.data_ptr())
 
 
 def quant_act_mx6(x_cl: torch.Tensor, geom, pre=None, ln=None, ups=False, lds=None):
     """dgq_quant_act_mx6 on the layer INPUT x_cl (channels-last storage, geom as for quant_act_block): one launch.  Returns (codes uint8
     [rows][C/32][24], scale uint8 [rows][lds] = E + 127 per 32-channel block) with rows = the input's rows / pixels (the SOURCE pixels
     with ``ups``); lds (default C/32) > C/32 adds entries of 127 (a Linear layer's K padding).  pre / ln / ups as in quant_act."""
-    B, H, W, C = geom[:4]
-    sh = 1 if ups else 0
-    rows = B * (H >> sh) * (W >> sh)
-    lds = C // 32 if lds is None else lds
-    a, keep = _quant_input(x_cl, geom, 6, pre, ln, ups)
-    codes = torch.empty((rows, C // 32, 24), dtype=torch.uint8, device=x_cl.device)
-    scale = torch.empty((rows, lds), dtype=torch.uint8, device=x_cl.device)
-    o = _lib.ActMx6Out()
-    o.codes, o.scale, o.lds = codes.data_ptr(), scale.data_ptr(), lds
-
-    def issue(_keep=(keep, codes, scale)):
-        _lib_call("dgq_quant_act_mx6", _c.byref(a), _c.byref(o), _lib.stream())
-    issue()
-    if BLOCK_LAUNCH_HOOK is not None:
-        BLOCK_LAUNCH_HOOK(issue, "quant", (rows, C))
-    return codes, scale
+    def outputs(rows, C, lds, dev):
+        codes = torch.empty((rows, C // 32, 24), dtype=torch.uint8, device=dev)
+        scale = torch.empty((rows, lds), dtype=torch.uint8, device=dev)
+        o = _lib.ActMx6Out()
+        o.codes, o.scale, o.lds = codes.data_ptr(), scale.data_ptr(), lds
+        return o, (codes, scale)
+    return _block_quant_launch("dgq_quant_act_mx6", x_cl, geom, 6, pre, ln, ups, lds, outputs)
 
 
 def dequant_act_mx6(codes, scale, out):
@@ -1017,29 +1025,9 @@ def dequant_act_mx6(codes, scale, out):
 def gemm_mx6(q, geom, ab: "MxActBinding", out_dtype, out=None, extra=None, ups=False):
     """One dgq_gemm_mx6 launch on q = quant_act_mx6(...) of the layer input; geom = (B, H, W, C, kh, kw, stride, pad) of the layer
     (H, W: behind a folded upsample).  Returns y [M][N] (N/2 columns with the GEGLU epilogue)."""
-    codes, scale = q
-    B, H, W, C, kh, kw, stride, pad = geom
-    M = B * ((H + 2 * pad - kh) // stride + 1) * ((W + 2 * pad - kw) // stride + 1)
-    pw = ab.pw
-    if out is None:
-        out = torch.empty((M, pw.N // 2 if (extra is not None and extra.geglu) else pw.N), dtype=out_dtype, device=codes.device)
-    g = _lib.GemmArgs()
-    g.codes, g.rowsum_parts = codes.data_ptr(), 1
-    g.M, g.Kp, g.wpacked, g.w_bits, g.N, g.per_m, g.L = M, ab.Kp, ab.wpacked.data_ptr(), 4, pw.N, 0, 1
-    g.alpha, g.gamma = pw.alpha.data_ptr(), ab.gamma.data_ptr()
-    g.y, g.y_dtype, g.ldy = out.data_ptr(), _lib.DTYPE_CODE[out.dtype], out.stride(0)
-    if extra is not None:
-        g.extra = _c.cast(_c.pointer(extra), _c.c_void_p)
     k = _lib.GemmMx6()
-    k.scale, k.lds = scale.data_ptr(), scale.shape[1]
-    k.B, k.H, k.W, k.C, k.kh, k.kw, k.stride, k.pad, k.ups = B, H, W, C, kh, kw, stride, pad, 1 if ups else 0
-
-    def issue(_keep=(q, out, extra, ab)):
-        _lib_call("dgq_gemm_mx6", _c.byref(g), _c.byref(k), _lib.stream())
-    issue()
-    if BLOCK_LAUNCH_HOOK is not None:
-        BLOCK_LAUNCH_HOOK(issue, "gemm", (M, pw.N, pw.K))
-    return out
+    k.scale, k.lds = q[1].data_ptr(), q[1].shape[1]
+    return _block_gemm_launch("dgq_gemm_mx6", k, q, geom, ab, out_dtype, out, extra, ups, w_bits=4)
 
 
 def _block_quant(ab, x_cl, geom, pre=None, ln=None, ups=False, pad_k=False):

@@ -1,7 +1,8 @@
 """Bit identity of the GEMM family across two library builds: prints `name sha256(output bytes)` for a few seconds of small cases that
 reach every kernel of gemm_wxa8.hip / gemm_wxa8_big.hip / gemm_panel.hip / gemm_convq.hip (and one attention call per kernel file
 that uses the XCD tile order) with REAL plan_act tables — flush coefficients that are not powers of two, which the exact-integer tests
-cannot see reordered.  Run it under each build (tools/ab_libs.sh "python tools/hash_gemm_family.py" old.so -) and diff the listings.
+cannot see reordered; a last section runs the real-time block family (gemm_blockq.hip, gemm_mx6.hip behind their quantisers) on random
+data.  Run it under each build (tools/ab_libs.sh "python tools/hash_gemm_family.py" old.so -) and diff the listings.
 usage: python tools/hash_gemm_family.py"""
 import hashlib, os, sys
 import torch
@@ -60,6 +61,56 @@ def linear(tag, M, N, K, plans, wbits=4, modes=("perK", "perM"), dtypes=("f32", 
                 env(DGQ_GEMM_FORCE=plan)
                 emit("%s M%d N%d K%d W%d %s %s plan %s" % (tag, M, N, K, wbits, mode, dt, plan), ops.quant_linear(xx, ab))
     env(DGQ_GEMM_FORCE=None)
+
+
+def block_layers():
+    """the real-time block family (quantiser + GEMM of each format: blockq W4 / W8, mx6) on random data — δ and scales that are no
+    powers of two: Linear layers (a K-padding tail; several row and column tiles), the convolution geometries of
+    tests/test_block_gather_cpu.py, the three output dtypes, each epilogue extra at one shape"""
+    g = torch.Generator().manual_seed(77)
+    dts = dict(DT, f16=torch.float16)
+
+    def formats(N, C, kh, kw):
+        out = []
+        for wbits in (4, 8):
+            w = torch.randn(N, C, *((kh, kw) if kh * kw > 1 else ()), generator=g) * 0.05
+            wd, wz = synth.channel_minmax(w, wbits)
+            pw = ops.PackedWeight(w.to(dev), wd.to(dev), wz.to(dev), None, torch.randn(N, generator=g).to(dev), wbits, C, kh * kw)
+            out.append(("blockq W%d" % wbits, ops.BlockActBinding(pw, 8)))
+            if wbits == 4:
+                out.append(("mx6", ops.MxActBinding(pw)))
+        return out
+
+    def run(ab, x, geom, ups, dtype, extra=None):
+        q = ops._block_quant(ab, x, geom, ups=ups, pad_k=geom[4:] == (1, 1, 1, 0))
+        return ops._block_gemm(ab, q, geom, dtype, extra=extra, ups=ups)
+
+    geoms = [("linear 37x320", (37, 1, 1, 320, 1, 1, 1, 0), 0), ("linear 154x768", (154, 1, 1, 768, 1, 1, 1, 0), 0),
+             ("conv 3x3 s1 p1 2x9x9x32", (2, 9, 9, 32, 3, 3, 1, 1), 0), ("conv 3x3 s2 p1 2x11x13x64", (2, 11, 13, 64, 3, 3, 2, 1), 0),
+             ("conv 3x3 ups 2x8x8x32", (2, 8, 8, 32, 3, 3, 1, 1), 1), ("conv 1x1 s2 p0 1x7x9x64", (1, 7, 9, 64, 1, 1, 2, 0), 0),
+             ("conv 3x3 p0 1x5x5x32", (1, 5, 5, 32, 3, 3, 1, 0), 0)]
+    for name, geom, ups in geoms:
+        B, H, W, C, kh, kw = geom[:6]
+        x = (torch.randn(B, H >> ups, W >> ups, C, generator=g) * 1.3 + 0.2).to(dev)
+        for N in ((24,) if name == "linear 37x320" else (320,) if name == "linear 154x768" else (24, 64)):
+            for fmt, ab in formats(N, C, kh, kw):
+                for dn, dt in dts.items():
+                    emit("block %s N%d %s %s" % (name, N, fmt, dn), run(ab, x, geom, ups, dt))
+    # ---- the extras: Linear 154 x 768 -> 320; GroupNorm partials on the ups convolution (M = 128)
+    M, K, N = 154, 768, 320
+    geom = (M, 1, 1, K, 1, 1, 1, 0)
+    x = (torch.randn(M, K, generator=g) * 1.3 + 0.2).to(dev)
+    res, res2 = torch.randn(M, N, generator=g).to(dev), torch.randn(M // 2, N, generator=g).to(dev)
+    cgeom = (2, 8, 8, 32, 3, 3, 1, 1)
+    xc = (torch.randn(2, 4, 4, 32, generator=g) * 1.3 + 0.2).to(dev)
+    for (fmt, ab), (_, abc) in zip(formats(N, K, 1, 1), formats(64, 32, 3, 3)):
+        emit("block extras %s residual" % fmt, run(ab, x, geom, 0, torch.float32, ops.make_extra(residual=res)))
+        emit("block extras %s residual res_div 2" % fmt, run(ab, x, geom, 0, torch.float32, ops.make_extra(residual=res2, res_div=2)))
+        emit("block extras %s GEGLU" % fmt, run(ab, x, geom, 0, torch.float32, ops.make_extra(geglu=True)))
+        buf = torch.zeros(M, N + 72, device=dev)
+        emit("block extras %s y2" % fmt, run(ab, x, geom, 0, torch.float32, ops.make_extra(y2=buf[:, 40:40 + N])), buf)
+        part = torch.zeros(128 // 16, 64, 2, device=dev)
+        emit("block extras %s GroupNorm partials" % fmt, run(abc, xc, cgeom, 1, torch.float32, ops.make_extra(gn_partial=part)), part)
 
 
 def main():
@@ -141,6 +192,8 @@ def main():
     for one in ("1", "0"):
         env(DGQ_ATTN_ONE=None if one == "1" else "0", DGQ_ATTN_SPLIT=None if one == "1" else "0")
         emit("attention D160 T64 S64 one-launch=%s" % one, ops.attention(q, k, v, H, D, D ** -0.5, 1, 0, None, 8, fq=fq))
+    env(DGQ_ATTN_ONE=None, DGQ_ATTN_SPLIT=None)
+    block_layers()
 
 
 main()

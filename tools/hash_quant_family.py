@@ -1,7 +1,8 @@
 """Bit identity of the activation-quantiser family across two library builds: prints `name sha256(output bytes)` for a few seconds of
 small cases that reach every kernel of quant_act.hip (each case asks dgq_quant_act_variant first and asserts the kernel it is named
-for), act_rowparams.hip and quant_block.hip, with REAL plan_act tables whose δ are no powers of two — a reordered per-K row sum shows.
-Hashed: codes and row sums; the (δ, z) tables of the row mode; codes, {δ, β} table, ρ and the dequantised x̂ of the block mode.
+for), act_rowparams.hip, quant_block.hip and quant_mx6.hip, with REAL plan_act tables whose δ are no powers of two — a reordered per-K
+row sum shows.  Hashed: codes and row sums; the (δ, z) tables of the row mode; codes, {δ, β} table, ρ and the dequantised x̂ of the block
+mode; codes, scales and x̂ of the MXFP6 mode.
 Run it under each build (tools/ab_libs.sh "python tools/hash_quant_family.py" old.so -) and diff the listings.
 usage: python tools/hash_quant_family.py [--plan]      --plan: print every case's kernel variant and launch nothing (needs no GPU)"""
 import ctypes, hashlib, os, sys, types
@@ -260,6 +261,28 @@ def block_cases():
             pre=groupnorm(2, 64, 45), ups=True)
 
 
+def mx6_cases():
+    # ---- dgq_quant_act_mx6 + dgq_dequant_act_mx6: block_cases' shapes and folds; lds > C/32; rows 3 and 7 carry an all-zero first block
+    def run(name, x, geom, pre=None, ln=None, ups=False, lds=None):
+        if PLAN:
+            return emit(name)
+        x = x.clone()
+        x.view(-1, x.shape[-1])[3:8:4, :32] = 0
+        codes, scale = ops.quant_act_mx6(x, geom, pre, ln, ups, lds)
+        xhat = ops.dequant_act_mx6(codes, scale, torch.empty((codes.shape[0], codes.shape[1] * 32), dtype=x.dtype, device=dev))
+        emit(name, codes, scale, xhat)
+    for dn, dt in DTYPES:
+        for C in (32, 320, 2048):
+            run("mx6 linear M203 C%d %s" % (C, dn), data((203, C), 50, dt), lin(203, C))
+            run("mx6 linear M203 C%d %s LayerNorm" % (C, dn), data((203, C), 50, dt), lin(203, C), ln=layernorm(C, 50))
+        run("mx6 linear M203 C320 %s lds 12" % dn, data((203, 320), 51, dt), lin(203, 320), lds=12)
+        run("mx6 linear M203 C320 %s GEGLU" % dn, data((203, 640), 52, dt), lin(203, 320), pre=(None, None, 2))
+        run("mx6 linear M203 C320 %s SiLU" % dn, data((203, 320), 53, dt), lin(203, 320), pre=(None, None, 1))
+        run("mx6 conv 2x9x9x64 3x3 %s GroupNorm+SiLU" % dn, data((2, 9, 9, 64), 54, dt), (2, 9, 9, 64, 3, 3, 1, 1), pre=groupnorm(2, 64, 54))
+        run("mx6 conv 2x10x10x64 3x3 %s ups GroupNorm+SiLU" % dn, data((2, 5, 5, 64), 55, dt), (2, 10, 10, 64, 3, 3, 1, 1),
+            pre=groupnorm(2, 64, 55), ups=True)
+
+
 if __name__ == "__main__":
-    for cases in (natural_cases, gather_cases, staged_cases, scatter_cases, conv_block_cases, row_params_cases, block_cases):
+    for cases in (natural_cases, gather_cases, staged_cases, scatter_cases, conv_block_cases, row_params_cases, block_cases, mx6_cases):
         cases()

@@ -44,7 +44,7 @@ def kernels(path, drops, renames=()):
         if ".amdhsa_kernel " + name not in s:
             continue
         dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
-        dem = re.sub(r'\((?!anonymous)[^()]*\)$', '', dem)
+        dem = re.sub(r'\((?!anonymous namespace\)$)(?:[^()]|\(anonymous namespace\))*\)$', '', dem)     # the parameter list
         for d in drops:
             kernel, text = d.split(":", 1)
             if kernel in dem:
