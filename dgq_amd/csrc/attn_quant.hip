@@ -18,6 +18,10 @@ __global__ __launch_bounds__(256) void fakequant_rows_kernel(const T* __restrict
             float d = delta[idx], z = zp[idx];
             float q = dgq_affine_code_fast(v, d, dgq_rcp(d), z, qmax);
             v = d * (q - z);
+            // the fp32 product is the statement (fp32(δ·(q − z)), then one rounding to the tensor's type).  Left to itself the compiler
+            // fuses this multiply with the __half conversion below into one v_fma_mixlo_f16, which rounds the exact product to f16
+            // directly: ~1e-4 of the fp16 outputs then differ by an f16 ulp from the fp32 formula (and from the fp32 / bf16 forms)
+            asm("" : "+v"(v));
         }
         y[i] = dgq_from_float<T>(v);
     }

@@ -3,8 +3,9 @@
 // and every calibration batch (quant/quant_layer.py:301-313): for a tensor viewed as [rows][C] these are the column-wise
 // and the row-wise min / max (the caller folds batch / head indices, which only repeat rows or columns).
 // One pass over x per statistic, HBM-bound, fp32 outputs; min / max are exact, so the results do not depend on the
-// reduction order.
-#include <cfloat>
+// reduction order.  The reductions start from ±inf, the identities of min / max, so a row or column that holds nothing
+// but +inf (−inf) reports it as torch.min / torch.max do.
+#include <cmath>
 #include "dgq_common.h"
 
 // row statistics: one wave per row, 4 elements per lane per step (rows are contiguous: ldx == C or 16-byte friendly)
@@ -15,7 +16,7 @@ __global__ __launch_bounds__(256) void row_minmax_kernel(const T* __restrict__ x
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const T* xr = x + (int64_t)row * ldx;
-    float lo = FLT_MAX, hi = -FLT_MAX;
+    float lo = INFINITY, hi = -INFINITY;
     for (int c = lane; c < C; c += 64) {
         const float v = dgq_to_float(xr[c]);
         lo = fminf(lo, v);
@@ -39,7 +40,7 @@ __global__ __launch_bounds__(256) void col_minmax_partial_kernel(const T* __rest
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
     const int r0 = blockIdx.y * rows_per_slice, r1 = min(rows, r0 + rows_per_slice);
-    float lo = FLT_MAX, hi = -FLT_MAX;
+    float lo = INFINITY, hi = -INFINITY;
     for (int r = r0; r < r1; ++r) {
         const float v = dgq_to_float(x[(int64_t)r * ldx + c]);
         lo = fminf(lo, v);
@@ -53,7 +54,7 @@ __global__ __launch_bounds__(256) void col_minmax_final_kernel(const float* __re
                                                                float* __restrict__ cmin, float* __restrict__ cmax) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
-    float lo = FLT_MAX, hi = -FLT_MAX;
+    float lo = INFINITY, hi = -INFINITY;
     for (int s = 0; s < slices; ++s) {
         lo = fminf(lo, part[((int64_t)s * 2 + 0) * C + c]);
         hi = fmaxf(hi, part[((int64_t)s * 2 + 1) * C + c]);

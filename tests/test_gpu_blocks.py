@@ -78,6 +78,70 @@ def test_f4_transformer_block_hip_vs_reference(case, fused, monkeypatch):
 
 
 @pytest.mark.parametrize("fused", [False, True], ids=["unfused", "fused"])
+@pytest.mark.parametrize("case", recipes.f4_tblock_cases(), ids=lambda c: c["name"])
+def test_f4_transformer_block_materialised_attention(case, fused, monkeypatch):
+    """The same blocks with no head dim in ops.ATTN_HEAD_DIMS, so that both attentions take the materialised branch of
+    quant_block.attention_forward (matmul -> softmax -> dgq_max_f32 / dgq_logquant_f32 or dgq_fakequant_rows -> matmul, q/k/v through
+    dgq_fakequant_rows): what calibration, reconstruction with gradients and other head dims run.  Same bound against f4_blocks.pt; the
+    spies prove the branch — the test cannot pass through the fused kernel.  The distance to the fused path's output is printed only."""
+    from dgq_amd import ops
+    from dgq_amd.diffusers_rewrite.unet import BasicTransformerBlock
+    from dgq_amd.quant import quant_block as qbm
+    from dgq_amd.quant.quant_layer import Scaler
+    monkeypatch.setattr(qbm, "FUSION", fused)
+    gold = torch.load(os.path.join(GOLD, "f4_blocks.pt"))["tblock_" + case["name"]]
+    inp = recipes.f4_tblock_inputs(case)
+    blk = BasicTransformerBlock(recipes.F4_HIDDEN, 768, heads=8)
+    blk.load_state_dict(inp["fp_sd"])
+    wq = {"bits": 4, "channel_wise": True, "scaler": Scaler.MINMAX}
+    aq = {"bits": case["abits"], "channel_wise": False, "scaler": Scaler.MINMAX, "leaf_param": True}
+    sm = {"softmax_a_bit": case["abits"], "t2i_log_quant": case["log"], "t2i_real_time": case["rt"],
+          "t2i_start_peak": case["sp"], "log_max_1": False}
+    _wrap_layers(blk, wq, aq, (nn.Linear,))
+    qb = qbm.QuantBasicTransformerBlock(blk, dict(aq), sm).cuda().eval()
+    _install(qb, gold)
+    qb.set_quant_state(True, True)
+    x, ctx = inp["x"].cuda(), inp["ctx"].cuda()
+    calls = {}
+
+    def spy(name):
+        orig = getattr(ops, name)
+
+        def wrapped(*a, **kw):
+            calls[name] = calls.get(name, 0) + 1
+            return orig(*a, **kw)
+        monkeypatch.setattr(ops, name, wrapped)
+    for name in ("attention", "fakequant_rows", "logquant_f32", "max_f32"):
+        spy(name)
+    head_dims = ops.ATTN_HEAD_DIMS
+    monkeypatch.setattr(ops, "ATTN_HEAD_DIMS", ())
+    with torch.no_grad():
+        y = qb(x, ctx)
+    torch.cuda.synchronize()
+    seen = dict(calls)
+    calls.clear()
+    monkeypatch.setattr(ops, "ATTN_HEAD_DIMS", head_dims)
+    with torch.no_grad():
+        y_fused_attn = qb(x, ctx)
+    torch.cuda.synchronize()
+    assert calls.get("attention", 0) == 2, calls                         # the comparison run did take the fused kernel
+    calls = seen
+    what = "transformer block %s (%s), materialised attention" % (case["name"], "fused" if fused else "unfused")
+    print("%s: ops calls %s" % (what, calls))
+    assert "attention" not in calls, calls
+    assert calls.get("fakequant_rows", 0) >= 6, calls                    # q, k, v of both attentions
+    if case["log"]:
+        assert calls.get("logquant_f32", 0) == 2, calls
+    if case["log"] and case["rt"]:
+        assert calls.get("max_f32", 0) == 2, calls
+    if not case["log"]:
+        assert calls.get("fakequant_rows", 0) == 8, calls                # ... and the uniform softmax quantiser of both
+    d = ((y.double() - y_fused_attn.double()).norm() / y_fused_attn.double().norm()).item()
+    print("%s: rel-L2 to the fused attention path's output %.3g (not asserted)" % (what, d))
+    _check(y, gold["y"], what)
+
+
+@pytest.mark.parametrize("fused", [False, True], ids=["unfused", "fused"])
 def test_f4_resnet_block_hip_vs_reference(fused, monkeypatch):
     """quant/quant_block.py:79-119 (reference QuantResnetBlock2D, grouped conv inputs) == dgq_amd QuantResnetBlock2D on the GPU"""
     from dgq_amd.diffusers_rewrite.unet import ResnetBlock2D

@@ -13,6 +13,7 @@ conv_block_pays), so the small images come in batches that reach that; the B = 1
 the planner gives them, which the spy records — next to the batch at which the tile in question launches.
 """
 import functools
+import math
 
 import pytest
 import torch
@@ -171,6 +172,127 @@ def test_rounding_ties(layout, dev, monkeypatch):
     quantise_and_check(dev, monkeypatch, case, d, q_rows, want_variant=5, want_tile=1)
     case, d, q_rows = cell(128, 128, 6, 6, 1, False, layout, 8, torch.float32, True)
     quantise_and_check(dev, monkeypatch, case, d, q_rows, want_variant=5, want_tile=1)
+
+
+# ---- general-δ ties.  With δ = 2^e the product x·(1/δ) of the quantisers' fast path is exact, so test_rounding_ties cannot see a wrong tie
+# band (dgq_affine_code_fast, dgq_common.h; dgq_affine_code4_fast, quant_common.h).  Here δ is log-uniform and x = fp32((n + ½)·δ) with its
+# ±1 / ±2 ulp neighbours: about a fifth of such values are exact ties of the fp32 quotient, the others lie one or two of ITS ulps beside
+# one (shares measured on the CPU by tests/test_standalone_kernels_ref_cpu.py) — inside the band, where only the IEEE division decides.
+def general_tables(case, layout, abits):
+    """``pow2_tables`` with δ log-uniform in [0.05, 2) instead of powers of two; Linear cases take their per-K table over K and their
+    per-M table over the M rows, in the shapes layer_reference.real_tables gives them."""
+    g = _gen("general tables", case["name"], layout, abits)
+    B, H, W, Ho, Wo, M, K, taps = lr.geometry(case)
+    lin = case["kind"] == "linear"
+    mid = 2 ** (abits - 1)
+    gd = torch.exp(torch.rand(G, generator=g, dtype=torch.float64) * (math.log(2.0) - math.log(0.05)) + math.log(0.05)).float()
+    gz = (mid + 2.0 * (torch.arange(G) - G // 2)).float()
+    gz[3], gz[11] = -3.0, float(2 ** abits + 2)
+    n = K if layout == "perK" else (M if lin else Ho * Wo)
+    labels = torch.randint(0, G, (n,), generator=g)
+    labels[:G] = torch.arange(G)[:n]
+    shape = {("perK", True): (1, 1, -1), ("perM", True): (1, -1, 1), ("perK", False): (1, -1, 1), ("perM", False): (1, 1, -1)}[(layout, lin)]
+    return gd[labels].view(shape), gz[labels].view(shape)
+
+
+def general_tie_input(case, layout, adelta, g):
+    """x on fp32((n + ½)·δ), |n| <= 9, and one or two ulps either side, a fifth each.  δ is the element's own (Linear), the one of the
+    element's centre tap (conv, per-K) or of the output position centred on the pixel (conv, per-M, stride 1): every value is on the
+    lattice of at least one of the quantisers that read it, and an ordinary value under the others."""
+    d = adelta.reshape(-1)
+    if case["kind"] == "linear":
+        M, K = case["M"], case["K"]
+        dc = (d.view(1, 1, K) if layout == "perK" else d.view(1, M, 1)).expand(1, M, K)
+    else:
+        B, C, H, W = case["B"], case["C"], case["H"], case["W"]
+        taps = case["k"] ** 2
+        assert case["stride"] == 1 and not case["upsample"]
+        dc = (d.view(1, C, taps, 1, 1)[:, :, taps // 2] if layout == "perK" else d.view(1, 1, H, W)).expand(B, C, H, W)
+    n = torch.randint(-9, 10, dc.shape, generator=g).double()
+    x = ((n + 0.5) * dc.double()).float()
+    side = torch.randint(0, 5, dc.shape, generator=g)
+    up, down = torch.full_like(x, float("inf")), torch.full_like(x, float("-inf"))
+    x1u, x1d = torch.nextafter(x, up), torch.nextafter(x, down)
+    for k, v in ((1, x1u), (2, x1d), (3, torch.nextafter(x1u, up)), (4, torch.nextafter(x1d, down))):
+        x = torch.where(side == k, v, x)
+    return x
+
+
+@functools.lru_cache(maxsize=None)
+def general_cell(kind, dims, layout, abits=8, N=32):
+    """One layer under ``general_tables`` on ``general_tie_input`` with its reference codes; asserts that exact ties of the fp32 quotient
+    and both kinds of neighbour occur among the codes inside the range."""
+    from dgq_amd import synth
+    from oracle import dgq_oracle as orc
+    case = lr.linear_case(*dims, N) if kind == "linear" else lr.conv_case(*dims, N)
+    g = _gen("general data", case["name"], layout, abits)
+    adelta, azp = general_tables(case, layout, abits)
+    x = general_tie_input(case, layout, adelta, g)
+    B, H, W, Ho, Wo, M, K, taps = lr.geometry(case)
+    lin = kind == "linear"
+    w = torch.randn((N, K) if lin else (N, case["C"], 3, 3), generator=g) * K ** -0.5
+    wd, wz = synth.channel_minmax(w, 4)
+    d = dict(x=x, w_raw=w, w=orc.uaq(w, wd, wz, 4), wdelta=wd, wzp=wz, bias=torch.randn(N, generator=g) * 0.1,
+             residual=torch.randn((1, M, N) if lin else (B, N, Ho, Wo), generator=g), adelta=adelta, azp=azp, abits=abits, wbits=4, layout=layout)
+    q, _ = lr.reference_codes(x, adelta, azp, abits, kind, case.get("k", 1), case.get("stride", 1), case.get("pad", 0), False)
+    cols = x if lin else torch.nn.functional.unfold(x, kernel_size=3, padding=1, stride=1)
+    t = (cols.double() / adelta.double()).float().double()
+    f = t - torch.floor(t)
+    live = (q > 0) & (q < 2 ** abits - 1)
+    for name, mask in (("exact ties", f == 0.5), ("values just above a tie", (f > 0.5) & (f < 0.5 + 1e-4)), ("values just below a tie", (f < 0.5) & (f > 0.5 - 1e-4))):
+        assert int((mask & live).sum()) >= 8, "%s %s: %d %s inside the code range" % (case["name"], layout, int((mask & live).sum()), name)
+    return case, d, lr.codes_rows(q, case)
+
+
+def quantise_and_check_codes(dev, monkeypatch, case, d, q_rows, want_variant):
+    """as test_real_layer_codes_and_output compares codes: torch.equal through kperm — no row-sum and no output claim (Σ δ·s is not exact
+    under a general δ)"""
+    from dgq_amd import _lib, ops
+    from dgq_amd.plan import natural_kperm
+    from tests.test_gpu_layer_routes import describe_code_mismatch
+    lay, ab = build_layer(ops, case, d, dev)
+    route = host_route(case, d)
+    assert route["variant"] == want_variant, "the planners send %s %s to variant %d, the cell is about variant %d: %s" % (
+        case["name"], d["layout"], route["variant"], want_variant, route)
+    spy = Spy(ops, _lib)
+    monkeypatch.setattr(ops, "_lib_call", spy)
+    codes, rowsum, folded = run_quantiser(ops, case, ab, d["x"].to(dev))
+    torch.cuda.synchronize()
+    qc = [c for c in spy.take() if c["name"] == "dgq_quant_act_batch"]
+    assert len(qc) == 1 and qc[0]["variant"] == want_variant, (qc, route)
+    B, H, W, Ho, Wo, M, K, taps = lr.geometry(case)
+    kperm = lay.kperm if lay.mode == "perK" else natural_kperm(K // taps, taps)
+    m = kperm >= 0
+    got, want = codes.cpu().int()[:, m], (q_rows[:, kperm[m].long()] - 2 ** (d["abits"] - 1)).int()
+    if not torch.equal(got, want):
+        raise AssertionError("%s %s variant %d: %s" % (case["name"], d["layout"], want_variant,
+                                                        describe_code_mismatch(case, got, want, kperm[m], route["tile"] if want_variant == 5 else 0)))
+    assert int(codes.cpu().int()[:, ~m].abs().sum()) == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["perK", "perM"])
+def test_rounding_ties_general_delta_conv(layout, dev, monkeypatch):
+    """conv variant 5 (c20_5x7, as test_rounding_ties) under a general δ"""
+    case, d, q_rows = general_cell("conv", (128, 20, 5, 7, 1), layout)
+    quantise_and_check_codes(dev, monkeypatch, case, d, q_rows, 5)
+
+
+#: one Linear cell per quantiser variant a Linear input can take (test_route_table_is_complete lists 0 .. 5; 5 is the block-staged conv
+#: path above): (variant, layout, M, K) with the smallest K at which quantiser_route gives the variant under ``general_tables`` (searched on
+#: the CPU: K in steps of 2 for variants 1 / 2, of 4 for the others; the route does not depend on M at these K — 1, 16, 64 and 256 rows give
+#: the same — and 64 rows make the lattice long enough to hold ties).  The cell's own host_route and the Spy confirm the variant.
+#:   1  per-K, K no multiple of 4: the table gather from global;  2  per-M: the natural order (K = 2 is refused: K % 4);
+#:   3  per-K, K % 4 == 0, padding of the groups >= K / 4;        0  per-K, K % 4 == 0, less padding than that: the staged strip;
+#:   4  per-K, K > 4096: too wide for a staged strip.
+LINEAR_VARIANT_CELLS = [(1, "perK", 64, 2), (2, "perM", 64, 4), (3, "perK", 64, 4), (0, "perK", 64, 824), (4, "perK", 64, 4100)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant,layout,M,K", LINEAR_VARIANT_CELLS, ids=lambda v: str(v))
+def test_rounding_ties_general_delta_linear(variant, layout, M, K, dev, monkeypatch):
+    case, d, q_rows = general_cell("linear", (M, K), layout)
+    quantise_and_check_codes(dev, monkeypatch, case, d, q_rows, variant)
 
 
 @pytest.mark.gpu
