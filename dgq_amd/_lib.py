@@ -58,6 +58,9 @@ SIGNATURES = {
     "dgq_dequant_act_mx6": [_vp, _vp, _i, _i64, _i, _vp, _i, _vp],
     "dgq_pack_w_mx6": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "dgq_gemm_mx6": [_vp, _vp, _vp],
+    "dgq_quant_act_mxint8": [_vp, _vp, _vp],
+    "dgq_dequant_act_mxint8": [_vp, _vp, _i, _i64, _i, _vp, _i, _vp],
+    "dgq_gemm_mxint8": [_vp, _vp, _vp],
     "dgq_gemm_wxa8_batch": [_i, _vp, _vp],
     "dgq_adaround_soft_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
     "dgq_adaround_soft_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
@@ -129,6 +132,16 @@ class GemmMx6(ctypes.Structure):
     """dgq_gemm_mx6_t of include/dgq_hip.h"""
     _fields_ = [("scale", _vp), ("lds", _i), ("B", _i), ("H", _i), ("W", _i), ("C", _i), ("kh", _i), ("kw", _i),
                 ("stride", _i), ("pad", _i), ("ups", _i)]
+
+
+class ActMxInt8Out(ctypes.Structure):
+    """dgq_act_mxint8_out_t of include/dgq_hip.h"""
+    _fields_ = ActMx6Out._fields_
+
+
+class GemmMxInt8(ctypes.Structure):
+    """dgq_gemm_mxint8_t of include/dgq_hip.h"""
+    _fields_ = GemmMx6._fields_
 
 
 class GemmArgs(ctypes.Structure):

@@ -51,9 +51,11 @@ def parse_args(argv=None):
     p.add_argument("--aq_real_time_block", type=int, default=0,
                    help="with --aq_real_time: 32 = one pair per row and block of 32 consecutive channels (dgq_quant_act_block + "
                         "dgq_gemm_blockq); 0 = one pair per row")
-    p.add_argument("--aq_real_time_format", default="int", choices=("int", "mxfp6"),
+    p.add_argument("--aq_real_time_format", default="int", choices=("int", "mxfp6", "mxint8"),
                    help="with --aq_real_time --aq_real_time_block 32 and 6 activation bits: mxfp6 = every block one power-of-two scale and "
-                        "32 FP6 E2M3 codes on the block-scaled matrix cores (dgq_quant_act_mx6 + dgq_gemm_mx6; W4 layers, W4A6)")
+                        "32 FP6 E2M3 codes on the block-scaled matrix cores (dgq_quant_act_mx6 + dgq_gemm_mx6; W4 layers, W4A6); with 8 "
+                        "activation bits: mxint8 = every block one power-of-two scale and 32 int8 codes, run as two E2M3 terms on the same "
+                        "cores (dgq_quant_act_mxint8 + dgq_gemm_mxint8; W4 layers, W4A8)")
     p.add_argument("--wq_mfma16", action="store_true",
                    help="weight-only state (no --use_aq): run the layers on the bf16 / f16 matrix cores (dgq_conv2d_wq_mfma16) — faster, "
                         "not bit-identical to the default exact route")
@@ -93,6 +95,9 @@ def main(argv=None):
     if opt.aq_real_time_format == "mxfp6" and not (opt.use_aq and opt.aq_real_time and opt.aq_real_time_block == 32 and opt.aq == 6):
         raise SystemExit("--aq_real_time_format mxfp6 is a format of the real-time block mode at 6 activation bits: it needs --use_aq "
                          "--aq_real_time --aq_real_time_block 32 and --aq 6")
+    if opt.aq_real_time_format == "mxint8" and not (opt.use_aq and opt.aq_real_time and opt.aq_real_time_block == 32 and opt.aq == 8):
+        raise SystemExit("--aq_real_time_format mxint8 is a format of the real-time block mode at 8 activation bits: it needs --use_aq "
+                         "--aq_real_time --aq_real_time_block 32 and --aq 8")
     logging.basicConfig(level=logging.INFO)
     from .diffusers_rewrite import UNet2DConditionModel, ARCH
     from .quant import get_qmodel, Scaler

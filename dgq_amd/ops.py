@@ -394,13 +394,18 @@ class MxActBinding(BlockActBinding):
     """The binding of a real-time MXFP6 activation quantizer (UniformAffineQuantizer(real_time=True, real_time_block=32,
     real_time_format="mxfp6")) on a layer whose weight is exact in FP6 E2M3 (PackedWeight.mx6_eligible): the MX weight image, bias and δw —
     no tables, no timestep slots, one binding per layer.  The routes of a block binding run it as dgq_quant_act_mx6 on the layer INPUT
-    (once per row / pixel: 24 code bytes and one E8M0 scale byte per 32-channel block) + dgq_gemm_mx6."""
+    (once per row / pixel: 24 code bytes and one E8M0 scale byte per 32-channel block) + dgq_gemm_mx6.  ``fmt`` carries the MX format:
+    real_time_format="mxint8" (8 bits) is the same binding on the MXINT8 entries."""
 
     mx = True
 
-    def __init__(self, pw: PackedWeight):
-        assert pw.C % 32 == 0, "real-time MXFP6 quantizer: C % 32 == 0"
-        self.mode, self.abits, self.offset = "block", 6, 0.0
+    def __init__(self, pw: PackedWeight, fmt: str = "mxfp6"):
+        """fmt "mxint8" (real_time_format="mxint8", 8 bits): the same weight image and eligibility under MXINT8 blocks — 48 code bytes
+        (two E2M3 planes of the int8 code) and one scale byte per block, dgq_quant_act_mxint8 + dgq_gemm_mxint8"""
+        assert pw.C % 32 == 0, "real-time MX quantizer: C % 32 == 0"
+        assert fmt in ("mxfp6", "mxint8")
+        self.fmt = fmt
+        self.mode, self.abits, self.offset = "block", 8 if fmt == "mxint8" else 6, 0.0
         self.pw = pw
         self.wpacked, self.Kp = pw.mx6()
         self.wfrag = None
@@ -1030,15 +1035,43 @@ def gemm_mx6(q, geom, ab: "MxActBinding", out_dtype, out=None, extra=None, ups=F
     return _block_gemm_launch("dgq_gemm_mx6", k, q, geom, ab, out_dtype, out, extra, ups, w_bits=4)
 
 
+def quant_act_mxint8(x_cl: torch.Tensor, geom, pre=None, ln=None, ups=False, lds=None):
+    """dgq_quant_act_mxint8 on the layer INPUT x_cl (as quant_act_mx6): one launch.  Returns (codes uint8 [rows][C/32][48] = the hi
+    plane's 24 bytes, then the lo plane's, scale uint8 [rows][lds] = E + 127 per 32-channel block)."""
+    def outputs(rows, C, lds, dev):
+        codes = torch.empty((rows, C // 32, 48), dtype=torch.uint8, device=dev)
+        scale = torch.empty((rows, lds), dtype=torch.uint8, device=dev)
+        o = _lib.ActMxInt8Out()
+        o.codes, o.scale, o.lds = codes.data_ptr(), scale.data_ptr(), lds
+        return o, (codes, scale)
+    return _block_quant_launch("dgq_quant_act_mxint8", x_cl, geom, 8, pre, ln, ups, lds, outputs)
+
+
+def dequant_act_mxint8(codes, scale, out):
+    """out [rows][C] = x̂ from quant_act_mxint8's codes and scales (dgq_dequant_act_mxint8)"""
+    rows, C = codes.shape[0], codes.shape[1] * 32
+    _lib_call("dgq_dequant_act_mxint8", _lib.ptr(codes), _lib.ptr(scale), scale.shape[1], rows, C, _lib.ptr(out), _lib.DTYPE_CODE[out.dtype],
+              _lib.stream())
+    return out
+
+
+def gemm_mxint8(q, geom, ab: "MxActBinding", out_dtype, out=None, extra=None, ups=False):
+    """One dgq_gemm_mxint8 launch on q = quant_act_mxint8(...) of the layer input; geom and the result as for gemm_mx6."""
+    k = _lib.GemmMxInt8()
+    k.scale, k.lds = q[1].data_ptr(), q[1].shape[1]
+    return _block_gemm_launch("dgq_gemm_mxint8", k, q, geom, ab, out_dtype, out, extra, ups, w_bits=4)
+
+
 def _block_quant(ab, x_cl, geom, pre=None, ln=None, ups=False, pad_k=False):
     """the input of a block binding quantised by its format's entry; pad_k: table / scale entries up to Kp/32 (Linear layers)"""
     if ab.mx:
-        return quant_act_mx6(x_cl, geom, pre, ln, ups, lds=ab.Kp // 32 if pad_k else None)
+        return (quant_act_mxint8 if ab.fmt == "mxint8" else quant_act_mx6)(x_cl, geom, pre, ln, ups, lds=ab.Kp // 32 if pad_k else None)
     return quant_act_block(x_cl, geom, ab.abits, pre, ln, ups, ldt=ab.Kp // 32 if pad_k else None)
 
 
 def _block_gemm(ab, q, geom, out_dtype, out=None, extra=None, ups=False):
-    return (gemm_mx6 if ab.mx else gemm_blockq)(q, geom, ab, out_dtype, out=out, extra=extra, ups=ups)
+    gemm = (gemm_mxint8 if ab.fmt == "mxint8" else gemm_mx6) if ab.mx else gemm_blockq
+    return gemm(q, geom, ab, out_dtype, out=out, extra=extra, ups=ups)
 
 
 def quant_linear(x: torch.Tensor, ab: ActBinding, pre_act=0, residual=None, fq=None, ln=None, geglu=False):

@@ -227,6 +227,37 @@ def mx6_unpack(packed: torch.Tensor):
     return torch.stack([(w >> (6 * j)) & 63 for j in range(4)], dim=-1).to(torch.uint8).view(R, -1)
 
 
+def mxint8_block(rows: torch.Tensor):
+    """The MXINT8 statement dgq_quant_act_mxint8 reproduces bit for bit (``real_time_format="mxint8"``): rows [R][C] fp32 (C % 32 == 0,
+    finite, behind any folded prologue), every 32 consecutive channels one block.  With amax = max |x′| of the block, E = floor(log2 amax)
+    — the OCP MX rule with the element emax 0, read off the exponent field of amax — clamped to [−120, 127] (so that 2^(6−E) and 2^(E−6)
+    are normal floats and both scalings exact), −120 for a zero or subnormal amax; s = clamp(rne(x′·2^(6−E)), −127, 127) — the symmetric
+    clamp: an amax just under a power of two rounds to 128 and saturates to 127.  Returns (codes int8 [R][C] = s, scale uint8 [R][C/32]
+    = E + 127, x̂ fp32 [R][C] = s·2^(E−6))."""
+    x = rows.detach().float()
+    R, C = x.shape
+    assert C % REAL_TIME_BLOCK == 0
+    xb = x.view(R, C // REAL_TIME_BLOCK, REAL_TIME_BLOCK)
+    amax = xb.abs().amax(dim=2)
+    field = (amax.contiguous().view(torch.int32) >> 23) & 0xFF              # 0 for zero and subnormal amax
+    E = torch.clamp(field - 127, min=-120)                                     # (finite amax: at most 127)
+    one = torch.ones_like(amax)
+    s = torch.clamp(torch.round(xb * torch.ldexp(one, 6 - E)[:, :, None]), min=-127.0, max=127.0)      # torch.round: half to even
+    xhat = (s * torch.ldexp(one, E - 6)[:, :, None]).view(R, C)
+    return s.to(torch.int8).view(R, C), (E + 127).to(torch.uint8), xhat
+
+
+def mxint8_split(codes: torch.Tensor):
+    """The two E2M3 code planes of MXINT8 codes s (int8, |s| <= 127): s = 16·h + l with h = s >> 4 in [−8, 7] and l = s & 15 in [0, 15];
+    both h/2 and l/2 are E2M3 grid values.  Returns (hi, lo) uint8 6-bit codes of the shape of ``codes``: hi = sign << 5 | magnitude code of
+    |h|/2 (h = 0 is stored +0), lo = the magnitude code of l/2.  ``mx6_pack`` packs each plane."""
+    s = codes.to(torch.int32)
+    h, l = s >> 4, s & 15
+    code = torch.tensor([E2M3_MAGNITUDES.index(n / 2.0) for n in range(16)], dtype=torch.int32, device=s.device)
+    hi = code[h.abs().long()] | torch.where(h < 0, 32, 0).to(torch.int32)
+    return hi.to(torch.uint8), code[l.long()].to(torch.uint8)
+
+
 def group_params_from_ranges(in_min, in_max, out_min, out_max, group_num, mode, level, force_in_channel=None):
     """The host half of ``done_group_num`` (quant_layer.py:338-418) as a pure function of the folded range vectors —
     returns (δ, z, in_channel_wise) in the checkpoint's broadcast shapes.  Arithmetic follows the reference line by
@@ -287,7 +318,12 @@ class UniformAffineQuantizer(nn.Module):
 
     ``real_time_format="mxfp6"`` (with ``real_time_block=32`` and 6 bits): the block is an OCP MXFP6 block instead — one power-of-two
     scale and 32 FP6 E2M3 codes (``mx6_block``), the operand of the block-scaled matrix cores (dgq_quant_act_mx6 + dgq_gemm_mx6).  W4
-    layers with integer zero points and C % 32 == 0 take it; every other layer runs as with ``real_time_block=32`` alone."""
+    layers with integer zero points and C % 32 == 0 take it; every other layer runs as with ``real_time_block=32`` alone.
+
+    ``real_time_format="mxint8"`` (with ``real_time_block=32`` and 8 bits): the block is an OCP MXINT8 block — one power-of-two scale
+    and 32 int8 codes (``mxint8_block``), each split exactly into two E2M3 terms (``mxint8_split``) for the same matrix cores
+    (dgq_quant_act_mxint8 + dgq_gemm_mxint8).  The same layers take it as take MXFP6; every other layer runs as with
+    ``real_time_block=32`` alone."""
 
     def __init__(self, bits: int = 8, symmetric: bool = False, channel_wise: bool = False,
                  scaler: Scaler = Scaler.MINMAX, leaf_param: bool = False, always_zero: bool = False,
@@ -300,10 +336,12 @@ class UniformAffineQuantizer(nn.Module):
         if real_time_block not in (0, REAL_TIME_BLOCK) or (real_time_block and not real_time):
             raise ValueError("real_time_block is 0 (one pair per row) or %d (one pair per row and block of %d consecutive channels), and a "
                              "granularity of real_time=True" % (REAL_TIME_BLOCK, REAL_TIME_BLOCK))
-        if real_time_format not in ("int", "mxfp6"):
-            raise ValueError("real_time_format is \"int\" or \"mxfp6\", not %r" % (real_time_format,))
+        if real_time_format not in ("int", "mxfp6", "mxint8"):
+            raise ValueError("real_time_format is \"int\", \"mxfp6\" or \"mxint8\", not %r" % (real_time_format,))
         if real_time_format == "mxfp6" and not (real_time and real_time_block == REAL_TIME_BLOCK and bits == 6):
             raise ValueError("real_time_format=\"mxfp6\" is a format of real_time=True with real_time_block=%d and bits=6" % REAL_TIME_BLOCK)
+        if real_time_format == "mxint8" and not (real_time and real_time_block == REAL_TIME_BLOCK and bits == 8):
+            raise ValueError("real_time_format=\"mxint8\" is a format of real_time=True with real_time_block=%d and bits=8" % REAL_TIME_BLOCK)
         self.real_time = bool(real_time)
         self.real_time_block = int(real_time_block)
         self.real_time_format = real_time_format
@@ -454,6 +492,11 @@ class UniformAffineQuantizer(nn.Module):
                     codes, scale = ops.quant_act_mx6(x2d, (x2d.shape[0], 1, 1, x2d.shape[1], 1, 1, 1, 0))
                     out = torch.empty_like(xc)
                     ops.dequant_act_mx6(codes, scale, out.view(x2d.shape))
+                    return out
+                if self.real_time_format == "mxint8":
+                    codes, scale = ops.quant_act_mxint8(x2d, (x2d.shape[0], 1, 1, x2d.shape[1], 1, 1, 1, 0))
+                    out = torch.empty_like(xc)
+                    ops.dequant_act_mxint8(codes, scale, out.view(x2d.shape))
                     return out
                 codes, table, _rho = ops.quant_act_block(x2d, (x2d.shape[0], 1, 1, x2d.shape[1], 1, 1, 1, 0), self.bits)
                 out = torch.empty_like(xc)
@@ -685,11 +728,13 @@ class QuantLayer(nn.Module):
         if self.aqtizer.real_time:                # no tables, no slots: one natural-order binding, its row tables made per call
             if "real_time" not in self._bindings:
                 # block granularity where the input channels split into whole 32-blocks; the per-row mode otherwise
-                # (MXFP6 blocks where the format asks for them and the weight is exact in E2M3)
+                # (MXFP6 / MXINT8 blocks where the format asks for them and the weight is exact in E2M3)
                 blk = self.aqtizer.real_time_block
                 whole = blk and self.in_channels % blk == 0
                 if whole and self.aqtizer.real_time_format == "mxfp6" and pw.mx6_eligible:
                     self._bindings["real_time"] = ops.MxActBinding(pw)
+                elif whole and self.aqtizer.real_time_format == "mxint8" and pw.mx6_eligible:
+                    self._bindings["real_time"] = ops.MxActBinding(pw, "mxint8")
                 else:
                     self._bindings["real_time"] = (ops.BlockActBinding(pw, self.aqtizer.bits) if whole
                                                    else ops.DynamicActBinding(pw, self.aqtizer.bits))

@@ -50,7 +50,8 @@ extern "C" {
  *        dgq_attention_mfma16_f32 (the same for fp32 tensors, every operand a two-term bf16 split); the real-time MXFP6 mode,
  *        dgq_quant_act_mx6 / dgq_dequant_act_mx6 / dgq_pack_w_mx6 / dgq_gemm_mx6 with dgq_act_mx6_out_t and dgq_gemm_mx6_t;
  *        dgq_conv2d_wq_mfma16_fused with its dgq_wq16_fuse_t — norms, SiLU, GEGLU and the residual folded into the weight-only
- *        matrix-core layer — and dgq_layernorm_row_stats */
+ *        matrix-core layer — and dgq_layernorm_row_stats; the real-time MXINT8 mode, dgq_quant_act_mxint8 / dgq_dequant_act_mxint8 /
+ *        dgq_gemm_mxint8 with dgq_act_mxint8_out_t and dgq_gemm_mxint8_t */
 #define DGQ_ABI_VERSION 123
 int dgq_version(void);
 const char* dgq_last_error(void);
@@ -470,6 +471,35 @@ typedef struct dgq_gemm_mx6 {
     int B, H, W, C, kh, kw, stride, pad, ups;
 } dgq_gemm_mx6_t;
 int dgq_gemm_mx6(const dgq_gemm_args_t* g, const dgq_gemm_mx6_t* mx, void* stream);
+
+/* ---- real-time MXINT8 activations on the block-scaled matrix cores (W4A8; a mode of this library) -------------------------------------
+ * Every block of DGQ_KCHUNK = 32 consecutive channels of every input row is an OCP MXINT8 block: ONE power-of-two scale and 32
+ * two's-complement codes s of value s·2^(E−6).  With amax = max |x′| of the block: E = floor(log2 amax) (the exponent field of amax; the
+ * OCP MX rule with the element emax 0), clamped to [−120, 127] so that 2^(6−E) and 2^(E−6) are normal floats, E = −120 for a zero or
+ * subnormal amax; s = clamp(rne(x′·2^(6−E)), −127, 127) (the symmetric clamp: an amax just under a power of two rounds to 128 and
+ * saturates to 127); x̂ = s·2^(E−6).  The statement is dgq_amd/quant/quant_layer.py mxint8_block.
+ * gfx950 has no MXINT8 operand type.  A code splits exactly into two FP6 E2M3 terms, s = 16·h + l with h = s >> 4 in [−8, 7] and
+ * l = s & 15 in [0, 15] — both h/2 and l/2 are E2M3 grid values (mxint8_split) — and the quantiser writes the two planes:
+ * dgq_quant_act_mxint8: `in` is read exactly as by dgq_quant_act_mx6.  ONE launch, no atomics, capture-safe:
+ *   codes [rows][C/32][48 bytes], 16-byte aligned: the hi plane's 24 bytes (sign-magnitude h/2; h = 0 is stored +0), then the lo plane's
+ *         (l/2), each the 192-bit little-endian string of a block's 6-bit codes as in dgq_act_mx6_out_t;
+ *   scale [rows][lds] E8M0 bytes E + 127, lds >= C/32; entries C/32 .. lds − 1 are written 127.
+ * dgq_dequant_act_mxint8: y [rows][C] (y_dtype) = (16h + l)·2^(E−6) from such codes and scales (one rounding into a 16-bit y).
+ * dgq_gemm_mxint8: y[m,n] = gamma[n] + alpha[n]·Σ_c 2^(E[m,c]−6)·Σ_{k∈c} s[m,k]·(q−z)[n,k]; per 64-deep K step two block-scaled FP6 MFMAs
+ * (lo plane, then hi plane) against the same weight fragment of dgq_pack_w_mx6's image — reused unchanged — under the block's scale byte
+ * and the constant weight-side bytes 123 / 127, ONE fp32 accumulator over the whole K, no K split, nothing exchanged between
+ * workgroups.  Every product is exact; only the fp32 accumulation rounds.  Arguments, rows, chunks, taps, ups and the Linear case as
+ * for dgq_gemm_mx6 (codes = this quantiser's; a tap outside the image contributes exactly 0; extra.conv and extra.act must be NULL). */
+typedef struct dgq_act_mxint8_out {
+    uint8_t* codes; uint8_t* scale; int lds;
+} dgq_act_mxint8_out_t;
+int dgq_quant_act_mxint8(const dgq_quant_act_args_t* in, const dgq_act_mxint8_out_t* out, void* stream);
+int dgq_dequant_act_mxint8(const uint8_t* codes, const uint8_t* scale, int lds, int64_t rows, int C, void* y, int y_dtype, void* stream);
+typedef struct dgq_gemm_mxint8 {
+    const uint8_t* scale; int lds;    /* dgq_act_mxint8_out_t.scale / lds */
+    int B, H, W, C, kh, kw, stride, pad, ups;
+} dgq_gemm_mxint8_t;
+int dgq_gemm_mxint8(const dgq_gemm_args_t* g, const dgq_gemm_mxint8_t* mx, void* stream);
 /* Small tile grids are split along K (deterministic: fp32 partial slabs [S][M][N] in the caller's `workspace`,
  * summed in a fixed order by a second kernel). dgq_gemm_workspace_bytes returns what the preferred split of a
  * shape needs; with workspace == NULL (or too small) fewer / no splits are used — results do not depend on it

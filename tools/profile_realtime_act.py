@@ -21,6 +21,10 @@ real-time modes, all in ALTERNATING rounds of hipGraph replays in one process on
 each mode against the same model with un-quantised activations.
 
     python tools/profile_realtime_act.py --mx --out profiles/r17_realtime_mxfp6.txt
+
+--mxint8 measures the real-time MXINT8 mode (real_time_format="mxint8": dgq_quant_act_mxint8 + dgq_gemm_mxint8, W4A8) the same way, against
+the int8 block and row modes — profiles/r22_realtime_mxint8.txt:
+    python tools/profile_realtime_act.py --mxint8 --out profiles/r22_realtime_mxint8.txt
 """
 import argparse
 import gc
@@ -136,10 +140,13 @@ def alternating_us(torch, graphs, rep=20, rounds=7):
     return {k: statistics.median(v) for k, v in out.items()}
 
 
-def mx_kernel_table(torch, ops, dev, lines):
-    """dgq_quant_act_mx6 + dgq_gemm_mx6 against dgq_quant_act_block + dgq_gemm_blockq and the row mode's layer call, A6, per SD layer shape"""
+def mx_kernel_table(torch, ops, dev, lines, fmt="mxfp6"):
+    """the MX quantiser + GEMM of ``fmt`` (mxfp6 at A6, mxint8 at A8) against dgq_quant_act_block + dgq_gemm_blockq and the row mode's layer
+    call at the same bit width, per SD layer shape"""
     from dgq_amd import synth
-    lines.append("layer shapes of an SD1.4 step (fp32, W4A6; 20 calls per hipGraph replay, median of 7 ALTERNATING rounds: mx quantiser, mx GEMM,")
+    ab = 8 if fmt == "mxint8" else 6
+    quant_mx, gemm_mx = (ops.quant_act_mxint8, ops.gemm_mxint8) if fmt == "mxint8" else (ops.quant_act_mx6, ops.gemm_mx6)
+    lines.append("layer shapes of an SD1.4 step (fp32, W4A%d; 20 calls" % ab + " per hipGraph replay, median of 7 ALTERNATING rounds: mx quantiser, mx GEMM,")
     lines.append("block quantiser, block GEMM, row-mode layer, mx quantiser, ...); mx / block = the two launches of the mode added")
     lines.append("%-34s %9s %9s %9s %9s %9s %9s %9s %9s" % ("layer", "mx q us", "mx g us", "mx us", "blk q us", "blk g us", "block us", "row us", "mx/block"))
     g = torch.Generator().manual_seed(0)
@@ -157,14 +164,14 @@ def mx_kernel_table(torch, ops, dev, lines):
         w = torch.randn(N, C * taps, generator=g) * (C * taps) ** -0.5
         wd, wz = synth.channel_minmax(w, 4)
         pw = ops.PackedWeight(w.to(dev), wd.to(dev), wz.to(dev), None, torch.zeros(N).to(dev), 4, C, taps)
-        mxb, blk, row = ops.MxActBinding(pw), ops.BlockActBinding(pw, 6), ops.DynamicActBinding(pw, 6)
+        mxb, blk, row = ops.MxActBinding(pw, fmt), ops.BlockActBinding(pw, ab), ops.DynamicActBinding(pw, ab)
         x = (torch.randn(B, H, W, C, generator=g) * 1.3 + 0.2).to(dev)
         pad_k = blk.Kp // 32 if taps == 1 else C // 32
-        qm, qb = ops.quant_act_mx6(x, geom, lds=pad_k), ops.quant_act_block(x, geom, 6, ldt=pad_k)
+        qm, qb = quant_mx(x, geom, lds=pad_k), ops.quant_act_block(x, geom, ab, ldt=pad_k)
         x2, xn = x.view(B * H * W, C), x.permute(0, 3, 1, 2)
         row_call = (lambda: ops.quant_linear(x2, row)) if taps == 1 else (lambda: ops.quant_conv2d(xn, row, kh, kw, stride, pad, gn_out=False))
-        graphs = dict(mq=captured(torch, lambda: ops.quant_act_mx6(x, geom, lds=pad_k)), mg=captured(torch, lambda: ops.gemm_mx6(qm, geom, mxb, torch.float32)),
-                      bq=captured(torch, lambda: ops.quant_act_block(x, geom, 6, ldt=pad_k)), bg=captured(torch, lambda: ops.gemm_blockq(qb, geom, blk, torch.float32)),
+        graphs = dict(mq=captured(torch, lambda: quant_mx(x, geom, lds=pad_k)), mg=captured(torch, lambda: gemm_mx(qm, geom, mxb, torch.float32)),
+                      bq=captured(torch, lambda: ops.quant_act_block(x, geom, ab, ldt=pad_k)), bg=captured(torch, lambda: ops.gemm_blockq(qb, geom, blk, torch.float32)),
                       row=captured(torch, row_call))
         us = alternating_us(torch, graphs)
         m, b = us["mq"] + us["mg"], us["bq"] + us["bg"]
@@ -172,7 +179,7 @@ def mx_kernel_table(torch, ops, dev, lines):
         if m > b:
             slower.append(name)
         del graphs
-    lines.append("shapes where the MXFP6 pair is slower than the block pair: %s" % (", ".join(slower) if slower else "none"))
+    lines.append("shapes where the MX pair is slower than the block pair: %s" % (", ".join(slower) if slower else "none"))
 
 
 def build_rt_model(torch, arch, fmt, abits, steps_cfg, batch, res, dev, use_aq=True):
@@ -193,8 +200,8 @@ def build_rt_model(torch, arch, fmt, abits, steps_cfg, batch, res, dev, use_aq=T
     aq["real_time"] = True
     if fmt != "row":
         aq["real_time_block"] = 32
-    if fmt == "mxfp6":
-        aq["real_time_format"] = "mxfp6"
+    if fmt in ("mxfp6", "mxint8"):
+        aq["real_time_format"] = fmt
     qnn = get_qmodel(arch, types.SimpleNamespace(unet=unet), path, wq, use_aq, aq, sm, False, steps_cfg, False, device=dev)
     qnn = qnn.float().to(dev)
     if use_aq:
@@ -204,10 +211,11 @@ def build_rt_model(torch, arch, fmt, abits, steps_cfg, batch, res, dev, use_aq=T
 
 
 MX_MODES = (("row", "real-time rows, A6"), ("block", "real-time blocks of 32, A6 (int)"), ("mxfp6", "real-time MXFP6 blocks, A6"))
+MXINT8_MODES = (("row", "real-time rows, A8"), ("block", "real-time blocks of 32, A8 (int)"), ("mxint8", "real-time MXINT8 blocks, A8"))
 
 
-def mx_step_table(torch, ops, args, dev, lines):
-    """the SD step in the three real-time modes at W4A6, alternating rounds of one process"""
+def mx_step_table(torch, ops, args, dev, lines, modes=MX_MODES, ab=6):
+    """the SD step in the three real-time modes at W4A6 (MXINT8_MODES: W4A8), alternating rounds of one process"""
     from dgq_amd import synth
     from dgq_amd.runtime import DDIMScheduler
     sched = DDIMScheduler(50).timesteps
@@ -217,8 +225,8 @@ def mx_step_table(torch, ops, args, dev, lines):
     lat = synth.named_randn("latent", (1, 4, 64, 64), 1).to(dev)
     ctx = synth.named_randn("ctx", (2, 77, 768), 100).to(dev)
     models, info = {}, {}
-    for mode, _label in MX_MODES:
-        qnn = build_rt_model(torch, "sd", mode, 6, 50, 2, 64, dev)
+    for mode, _label in modes:
+        qnn = build_rt_model(torch, "sd", mode, ab, 50, 2, 64, dev)
 
         def one_step(x, t, qnn=qnn):
             eps = qnn(torch.cat([x, x], dim=0), t, ctx)[0]
@@ -240,7 +248,7 @@ def mx_step_table(torch, ops, args, dev, lines):
         models[mode], info[mode] = one_step, (len(calls), by, [])
     with torch.no_grad():
         for _ in range(args.windows):
-            for mode, _label in MX_MODES:
+            for mode, _label in modes:
                 x = lat
                 for t in timesteps[:args.warmup]:
                     x = models[mode](x, t)
@@ -251,26 +259,26 @@ def mx_step_table(torch, ops, args, dev, lines):
                 torch.cuda.synchronize()
                 info[mode][2].append((time.perf_counter() - t0) / args.steps * 1e3)
                 assert torch.isfinite(x).all()
-    lines += ["", "SD1.4-size synthetic model, 512^2 (64x64 latents), CFG pair, fp32, W4A6, weight-only checkpoint; hipGraph replay, %d timed steps behind"
-              % args.steps, "%d warm-up steps per window, %d ALTERNATING rounds (rows, blocks, mxfp6, rows, ...) in one process on one box" % (args.warmup, args.windows),
+    lines += ["", "SD1.4-size synthetic model, 512^2 (64x64 latents), CFG pair, fp32, W4A%d, weight-only checkpoint; hipGraph replay, %d timed steps behind"
+              % (ab, args.steps), "%d warm-up steps per window, %d ALTERNATING rounds (rows, blocks, MX blocks, rows, ...) in one process on one box" % (args.warmup, args.windows),
               "%-44s %10s %10s %10s %12s" % ("mode", "median ms", "min ms", "max ms", "entry calls")]
-    for mode, label in MX_MODES:
+    for mode, label in modes:
         ncalls, by, ms = info[mode]
         lines.append("%-44s %10.3f %10.3f %10.3f %12d" % (label, statistics.median(ms), min(ms), max(ms), ncalls))
     lines += ["", "entry calls = calls of libdgq_hip.so entries in one eager step, by entry:"]
-    lines += ["%s: %s" % (mode, ", ".join("%s %d" % kv for kv in sorted(info[mode][1].items(), key=lambda kv: -kv[1]))) for mode, _ in MX_MODES]
+    lines += ["%s: %s" % (mode, ", ".join("%s %d" % kv for kv in sorted(info[mode][1].items(), key=lambda kv: -kv[1]))) for mode, _ in modes]
 
 
-def mx_tiny_error(torch, dev, lines):
-    """rel-L2 of the tiny UNet's output in each real-time mode at W4A6 against the same weights with UN-QUANTISED activations"""
+def mx_tiny_error(torch, dev, lines, modes=MX_MODES, ab=6):
+    """rel-L2 of the tiny UNet's output in each real-time mode at W4A6 (MXINT8_MODES: W4A8) against the same weights with UN-QUANTISED activations"""
     from dgq_amd import synth
     inp = synth.synth_inputs("tiny", 2, 1, 16)
     x, ctx = inp["sample"].to(dev), inp["encoder_hidden_states"].to(dev)
     with torch.no_grad():
-        ref = build_rt_model(torch, "tiny", "row", 6, 25, 2, 16, dev, use_aq=False)(x, torch.tensor(999), ctx)[0].double()
-        lines += ["", "tiny UNet (weight-only checkpoint, W4A6, t = 999): rel-L2 of the output against the same weights with un-quantised activations"]
-        for mode, label in MX_MODES:
-            y = build_rt_model(torch, "tiny", mode, 6, 25, 2, 16, dev)(x, torch.tensor(999), ctx)[0].double()
+        ref = build_rt_model(torch, "tiny", "row", ab, 25, 2, 16, dev, use_aq=False)(x, torch.tensor(999), ctx)[0].double()
+        lines += ["", "tiny UNet (weight-only checkpoint, W4A%d, t = 999)" % ab + ": rel-L2 of the output against the same weights with un-quantised activations"]
+        for mode, label in modes:
+            y = build_rt_model(torch, "tiny", mode, ab, 25, 2, 16, dev)(x, torch.tensor(999), ctx)[0].double()
             lines.append("%-44s %10.4g" % (label, float((y - ref).norm() / ref.norm())))
 
 
@@ -423,7 +431,8 @@ def main(argv=None):
     ap.add_argument("--kernels-only", action="store_true")
     ap.add_argument("--block", action="store_true", help="measure the real-time block mode (see the head of this file)")
     ap.add_argument("--mx", action="store_true", help="measure the real-time MXFP6 mode (see the head of this file)")
-    ap.add_argument("--append", default=None, help="--mx: a text file whose lines are appended to the report (the tests' measured constants)")
+    ap.add_argument("--mxint8", action="store_true", help="measure the real-time MXINT8 mode (see the head of this file)")
+    ap.add_argument("--append", default=None, help="--mx / --mxint8: a text file whose lines are appended to the report (the tests' measured constants)")
     args = ap.parse_args(argv)
     import torch
     from dgq_amd import _lib, ops
@@ -431,13 +440,15 @@ def main(argv=None):
     _lib.require_gpu()
     torch.set_num_threads(min(torch.get_num_threads(), 16))
     dev = torch.device("cuda", 0)
-    if args.mx:
-        lines = ["real-time MXFP6 activation mode (real_time_format=\"mxfp6\", W4A6) — tools/profile_realtime_act.py --mx",
+    if args.mx or args.mxint8:
+        fmt, modes, ab = ("mxint8", MXINT8_MODES, 8) if args.mxint8 else ("mxfp6", MX_MODES, 6)
+        lines = ["real-time %s activation mode (real_time_format=\"%s\", W4A%d) — tools/profile_realtime_act.py --%s"
+                 % (fmt.upper(), fmt, ab, "mxint8" if args.mxint8 else "mx"),
                  "commit %s; %s; torch %s; ABI %d" % (args.stamp or stamp_default(), torch.cuda.get_device_name(0), torch.__version__, _lib.ABI_VERSION), ""]
-        mx_kernel_table(torch, ops, dev, lines)
-        mx_tiny_error(torch, dev, lines)
+        mx_kernel_table(torch, ops, dev, lines, fmt)
+        mx_tiny_error(torch, dev, lines, modes, ab)
         if not args.kernels_only:
-            mx_step_table(torch, ops, args, dev, lines)
+            mx_step_table(torch, ops, args, dev, lines, modes, ab)
         if args.append:
             lines += [""] + open(args.append).read().splitlines()
         text = "\n".join(lines) + "\n"
