@@ -61,6 +61,10 @@ SIGNATURES = {
     "dgq_quant_act_mxint8": [_vp, _vp, _vp],
     "dgq_dequant_act_mxint8": [_vp, _vp, _i, _i64, _i, _vp, _i, _vp],
     "dgq_gemm_mxint8": [_vp, _vp, _vp],
+    "dgq_gemm_mx6_splitk": [_vp, _vp, _i, _vp, ctypes.c_size_t, _vp],
+    "dgq_gemm_mxint8_splitk": [_vp, _vp, _i, _vp, ctypes.c_size_t, _vp],
+    "dgq_gemm_mx_plan_splits": [_i, _i, _i, ctypes.c_size_t],
+    "dgq_gemm_mx_workspace_bytes": [_i, _i, _i],
     "dgq_gemm_wxa8_batch": [_i, _vp, _vp],
     "dgq_adaround_soft_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
     "dgq_adaround_soft_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],

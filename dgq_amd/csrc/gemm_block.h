@@ -63,6 +63,31 @@ __device__ __forceinline__ void block_store(const GemmParams& p, uint8_t* smem, 
     DGQ_STAMP(10); DGQ_STAMP_REAL(11);
 }
 
+// ---- The K split of the block-scaled formats (gemm_mx6.hip, gemm_mxint8.hip; the combine and the plan: gemm_mx_split.hip).  Split s =
+// blockIdx.z of a tile walks K tiles [s·tps, min((s + 1)·tps, nkt)) and leaves, instead of block_store, each wave's raw accumulator in
+// the caller's workspace in the accumulator's own order, [split][tile_m][tile_n][wave][reg / 4][lane] as float4: 16-byte stores, a
+// wave's 64 lanes on 1 KiB in a row, no LDS transposition, no epilogue.  32 KiB per tile and split, ragged tiles whole; the two K waves
+// of a tile stay apart (2S partials per output tile).  The combine — a launch of its own on the tile grid, the kernel boundary is the
+// only exchange — adds each wave's S partials in split order and runs the family's block_store on the sum: one fixed summation order
+// (s ascending inside a K wave, then K wave 0 before 1 as un-split), every epilogue form, no atomics, no counters.
+struct BlockSplit { float4* slab; int tps; };               // the partials; K tiles per split
+constexpr int BLK_PART4 = BLK_NW * 4 * 64;                   // float4 per (tile, split)
+constexpr size_t BLK_PART_BYTES = (size_t)BLK_PART4 * 16;
+
+// first float4 of wave r.wid, lane r.lane in the partial of this workgroup's tile under split s; register quad j sits at + 64·j
+__device__ __forceinline__ int64_t block_partial_at(const BlockRoles& r, int s) {
+    return ((((int64_t)s * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * BLK_NW + r.wid) * (4 * 64) + r.lane;
+}
+__device__ __forceinline__ void block_store_partial(const BlockSplit& z, const BlockRoles& r, const v16f& acc) {
+    float4* dst = z.slab + block_partial_at(r, blockIdx.z);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dst[64 * j] = make_float4(acc[4 * j], acc[4 * j + 1], acc[4 * j + 2], acc[4 * j + 3]);
+}
+
+// gemm_mx_split.hip: the plan for nkt K tiles (1 = un-split) and the combine launch behind a split one
+int block_split_plan(int M, int N, int nkt, size_t workspace_bytes);
+int block_combine_launch(const char* who, const GemmParams& p, const BlockSplit& z, int splits, int y_dtype, hipStream_t st);
+
 // The shared part of a block entry: checks of the problem, the geometry and the extras; GemmParams and the gather.  zero_point: the
 // format has zero-point terms (row sums, zw, offset); without, the epilogue runs with R = 0 and zw = 0 and the three are not read.
 static inline int block_gemm_setup(const char* who, const dgq_gemm_args_t& a, int B, int H, int W, int C, int kh, int kw, int stride, int pad, int ups,
@@ -110,4 +135,27 @@ static int block_gemm_launch(const char* who, const GemmParams& p, const BlockGa
         default: dgq_set_error("%s: unknown y dtype %d", who, y_dtype); return DGQ_EINVAL;
     }
     return dgq_launch_status(who);
+}
+
+// The launch of a *_splitk entry.  splits: 0 = the plan's choice, >= 1 forced; either is clamped to the K tiles and to what the
+// workspace holds (none: 1), and no split is empty.  One split is the un-split kernel.  Kernel::split = the split instance taking
+// (GemmParams, BlockGather, Operand, BlockSplit): it has no epilogue, hence no output dtype.
+template <typename Kernel, typename Operand>
+static int block_gemm_launch_split(const char* who, const GemmParams& p, const BlockGather& q, const Operand& o, int y_dtype, int splits,
+                                   void* workspace, size_t workspace_bytes, hipStream_t st) {
+    DGQ_CHECK_ARG(splits >= 0, "%s: splits=%d", who, splits);
+    DGQ_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+    DGQ_CHECK_ARG(y_dtype == DGQ_F32 || y_dtype == DGQ_F16 || y_dtype == DGQ_BF16, "%s: unknown y dtype %d", who, y_dtype);
+    const dim3 tiles((p.N + BLK_BN - 1) / BLK_BN, (p.M + BLK_BM - 1) / BLK_BM);
+    const int nkt = (q.nch + BLK_CH - 1) / BLK_CH;
+    const size_t bytes = workspace ? workspace_bytes : 0, fit = bytes / ((size_t)tiles.x * tiles.y * BLK_PART_BYTES);
+    int s = splits == 0 ? block_split_plan(p.M, p.N, nkt, bytes) : splits;
+    s = s > nkt ? nkt : s;
+    s = (size_t)s > fit ? (int)fit : s;
+    if (s <= 1) return block_gemm_launch<Kernel>(who, p, q, o, y_dtype, st);
+    BlockSplit z = {reinterpret_cast<float4*>(workspace), (nkt + s - 1) / s};
+    s = (nkt + z.tps - 1) / z.tps;                          // no empty split
+    if (s == 1) return block_gemm_launch<Kernel>(who, p, q, o, y_dtype, st);
+    hipLaunchKernelGGL(Kernel::split, dim3(tiles.x, tiles.y, s), dim3(BLK_NT), 0, st, p, q, o, z);
+    return block_combine_launch(who, p, z, s, y_dtype, st);
 }

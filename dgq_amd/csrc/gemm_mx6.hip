@@ -17,7 +17,9 @@
 // scale byte and the weight piece of its (row, chunk); one MFMA covers the chunk pair (2i, 2i + 1), one chunk per lane half.  Chunk c =
 // tap·(C/32) + cb of output row m reads pixel (ho·stride − pad + dh, wo·stride − pad + dw) (>> ups); a tap outside the image (and the K
 // padding) stages zero codes under the scale 2^0 and contributes exactly 0.  The LDS images keep 32 bytes per (row, chunk) — a lane
-// reads 16 + 8 of them, as gemm_blockq.hip's fragment reads are spaced; the HBM images stay at 24.  No K split, no atomics.
+// reads 16 + 8 of them, as gemm_blockq.hip's fragment reads are spaced; the HBM images stay at 24.  No atomics.  dgq_gemm_mx6 walks the whole K
+// in one workgroup per tile; dgq_gemm_mx6_splitk runs the same walk over 1/S of the K tiles per workgroup (blockIdx.z = split) and leaves raw
+// accumulators for the family's combine launch (gemm_block.h, gemm_mx_split.hip) — the long-K low-M convolutions, by the plan there.
 #include "gemm_block.h"
 
 DGQ_DIAG_BUFFER(mx6)
@@ -32,8 +34,10 @@ constexpr int MX_A = BLK_CH * BLK_BM * 32, MX_W = BLK_CH * BLK_BN * 32;  // [chu
 constexpr int MX_SC = BLK_CH * BLK_BM;                                   // [chunk][row] scale bytes
 constexpr int MX_RING = block_ring(MX_A + MX_W + MX_SC);
 
-template <typename TOut>
-__global__ __launch_bounds__(BLK_NT) void gemm_mx6_kernel(GemmParams p, BlockGather q, Mx6Operand o) {
+// One workgroup's walk: un-split (SPLIT false) the whole K and the store epilogue; split, K tiles [blockIdx.z·z.tps, + z.tps) and the raw
+// accumulators into z.slab (gemm_block.h) — the gather, the staging, the LDS images and the MFMA steps are the same text.
+template <typename TOut, bool SPLIT>
+__device__ __forceinline__ void gemm_mx6_tile(const GemmParams& p, const BlockGather& q, const Mx6Operand& o, const BlockSplit& z) {
     __shared__ __attribute__((aligned(16))) uint8_t smem[MX_RING + BLK_VEC];
     DGQ_DIAG_DECL
     DGQ_STAMP(0); DGQ_STAMP_REAL(1); DGQ_STAMP_WHERE(2);
@@ -50,7 +54,7 @@ __global__ __launch_bounds__(BLK_NT) void gemm_mx6_kernel(GemmParams p, BlockGat
     const int64_t apitch = (int64_t)q.cpb * 24;             // code bytes per pixel
 
     // ---- epilogue vectors: no row terms (R = 0), the column constants with zw = 0
-    if (r.tid < BLK_BM) block_vectors(vtab, vtab + 3 * BLK_BM, r.tid, p, n, 0.0f, 0.0f);
+    if (!SPLIT && r.tid < BLK_BM) block_vectors(vtab, vtab + 3 * BLK_BM, r.tid, p, n, 0.0f, 0.0f);
 
     // ---- staging registers of one K tile
     uint2 ra0, ra1, ra2, rw0, rw1, rw2;
@@ -82,11 +86,12 @@ __global__ __launch_bounds__(BLK_NT) void gemm_mx6_kernel(GemmParams p, BlockGat
 #pragma unroll
     for (int i = 0; i < 16; ++i) accf[0][0][i] = 0.0f;
     const int nkt = (q.nch + BLK_CH - 1) / BLK_CH;
-    load_tile(0);
-    for (int kt = 0; kt < nkt; ++kt) {
+    const int kt0 = SPLIT ? (int)blockIdx.z * z.tps : 0, kt1 = SPLIT ? min(kt0 + z.tps, nkt) : nkt;
+    load_tile(kt0);
+    for (int kt = kt0; kt < kt1; ++kt) {
         store_tile();
         __syncthreads();
-        if (kt + 1 < nkt) load_tile(kt + 1);
+        if (kt + 1 < kt1) load_tile(kt + 1);
 #pragma unroll
         for (int ii = 0; ii < BLK_CH / 4; ++ii) {
             const int pr = 2 * ii + r.wave_k;               // this K wave's chunk pairs of the tile
@@ -105,11 +110,23 @@ __global__ __launch_bounds__(BLK_NT) void gemm_mx6_kernel(GemmParams p, BlockGat
         }
         __syncthreads();
     }
-    block_store<TOut, MX_RING>(p, smem, r, nkt, accf DGQ_DIAG_ARG);
+    if constexpr (SPLIT) block_store_partial(z, r, accf[0][0]);
+    else block_store<TOut, MX_RING>(p, smem, r, nkt, accf DGQ_DIAG_ARG);
     DGQ_DIAG_FLUSH(mx6, BLK_NW, r.wid, r.lane);
 }
 
-struct Mx6Kernel { template <typename TOut> static constexpr auto fn = gemm_mx6_kernel<TOut>; };
+template <typename TOut>
+__global__ __launch_bounds__(BLK_NT) void gemm_mx6_kernel(GemmParams p, BlockGather q, Mx6Operand o) {
+    gemm_mx6_tile<TOut, false>(p, q, o, BlockSplit{});
+}
+__global__ __launch_bounds__(BLK_NT) void gemm_mx6_split_kernel(GemmParams p, BlockGather q, Mx6Operand o, BlockSplit z) {
+    gemm_mx6_tile<float, true>(p, q, o, z);
+}
+
+struct Mx6Kernel {
+    template <typename TOut> static constexpr auto fn = gemm_mx6_kernel<TOut>;
+    static constexpr auto split = gemm_mx6_split_kernel;
+};
 
 // E2M3 code of h = (q − z)/2 for an integer d = q − z, |d| <= 15: every such h is a grid value (0.5 is the subnormal 4/8; 1 .. 7.5 in
 // steps of 0.5 have at most 3 mantissa bits), so the code is read off the float's exponent and top mantissa bits, no rounding
@@ -161,15 +178,33 @@ extern "C" int dgq_pack_w_mx6(const uint8_t* codes, const float* zw, int N, int 
     return dgq_launch_status("dgq_pack_w_mx6");
 }
 
-extern "C" int dgq_gemm_mx6(const dgq_gemm_args_t* g, const dgq_gemm_mx6_t* mx, void* stream) {
-    const char* who = "dgq_gemm_mx6";
-    DGQ_CHECK_ARG(g && mx && mx->scale, "dgq_gemm_mx6: null pointer");
+// what both entries do in front of their launch: the family's set-up and this format's operand
+static int gemm_mx6_setup(const char* who, const dgq_gemm_args_t* g, const dgq_gemm_mx6_t* mx, GemmParams& p, BlockGather& q, Mx6Operand& o) {
+    DGQ_CHECK_ARG(g && mx && mx->scale, "%s: null pointer", who);
     const dgq_gemm_mx6_t& k = *mx;
-    GemmParams p;
-    BlockGather q;
     const int rc = block_gemm_setup(who, *g, k.B, k.H, k.W, k.C, k.kh, k.kw, k.stride, k.pad, k.ups, false, p, q);
     if (rc != DGQ_OK) return rc;
-    DGQ_CHECK_ARG(k.lds >= q.cpb, "dgq_gemm_mx6: scale pitch %d < %d blocks", k.lds, q.cpb);
-    const Mx6Operand o = {k.scale, k.lds};
+    DGQ_CHECK_ARG(k.lds >= q.cpb, "%s: scale pitch %d < %d blocks", who, k.lds, q.cpb);
+    o = {k.scale, k.lds};
+    return DGQ_OK;
+}
+
+extern "C" int dgq_gemm_mx6(const dgq_gemm_args_t* g, const dgq_gemm_mx6_t* mx, void* stream) {
+    const char* who = "dgq_gemm_mx6";
+    GemmParams p;
+    BlockGather q;
+    Mx6Operand o;
+    const int rc = gemm_mx6_setup(who, g, mx, p, q, o);
+    if (rc != DGQ_OK) return rc;
     return block_gemm_launch<Mx6Kernel>(who, p, q, o, g->y_dtype, (hipStream_t)stream);
+}
+
+extern "C" int dgq_gemm_mx6_splitk(const dgq_gemm_args_t* g, const dgq_gemm_mx6_t* mx, int splits, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "dgq_gemm_mx6_splitk";
+    GemmParams p;
+    BlockGather q;
+    Mx6Operand o;
+    const int rc = gemm_mx6_setup(who, g, mx, p, q, o);
+    if (rc != DGQ_OK) return rc;
+    return block_gemm_launch_split<Mx6Kernel>(who, p, q, o, g->y_dtype, splits, workspace, workspace_bytes, (hipStream_t)stream);
 }

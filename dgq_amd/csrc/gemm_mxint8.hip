@@ -15,8 +15,9 @@
 // stays.  Thread (row = tid & 63, chunk = tid >> 6) stages the 48 code bytes (three 16-byte loads), the scale byte and the 24 weight
 // bytes of its (row, chunk).  The LDS image is 64 bytes per activation (row, chunk), each plane on its own 32 bytes (24 used) in a
 // plane-major array, so a lane's 16 + 8 byte fragment reads are spaced as gemm_mx6.hip's, and 32 bytes per weight (row, chunk).  A tap
-// outside the image (and the K padding) stages zero codes under the scale 2^0 and contributes exactly 0.  No K split, no atomics: the
-// long-K low-M shapes keep gemm_mx6.hip's known weakness (few workgroups, each walking the whole K).
+// outside the image (and the K padding) stages zero codes under the scale 2^0 and contributes exactly 0.  No atomics.  dgq_gemm_mxint8
+// walks the whole K in one workgroup per tile; dgq_gemm_mxint8_splitk is gemm_mx6.hip's K split on this format's walk (same partial layout,
+// same combine kernel and plan: gemm_block.h, gemm_mx_split.hip) for the long-K low-M shapes.
 #include "gemm_block.h"
 
 DGQ_DIAG_BUFFER(mxint8)
@@ -34,8 +35,10 @@ constexpr int MXI_RING = block_ring(MXI_A + MXI_W + MXI_SC);
 static_assert(MXI_RING + BLK_VEC <= 64 * 1024, "the 8-chunk tile within the static LDS");
 constexpr int MXI_SB_LO = 123, MXI_SB_HI = 127;                // scale_b of the lo / hi plane (see above)
 
-template <typename TOut>
-__global__ __launch_bounds__(BLK_NT) void gemm_mxint8_kernel(GemmParams p, BlockGather q, MxInt8Operand o) {
+// One workgroup's walk: un-split (SPLIT false) the whole K and the store epilogue; split, K tiles [blockIdx.z·z.tps, + z.tps) and the raw
+// accumulators into z.slab (gemm_block.h) — the gather, the staging, the LDS images and the MFMA steps are the same text.
+template <typename TOut, bool SPLIT>
+__device__ __forceinline__ void gemm_mxint8_tile(const GemmParams& p, const BlockGather& q, const MxInt8Operand& o, const BlockSplit& z) {
     __shared__ __attribute__((aligned(16))) uint8_t smem[MXI_RING + BLK_VEC];
     DGQ_DIAG_DECL
     DGQ_STAMP(0); DGQ_STAMP_REAL(1); DGQ_STAMP_WHERE(2);
@@ -53,7 +56,7 @@ __global__ __launch_bounds__(BLK_NT) void gemm_mxint8_kernel(GemmParams p, Block
     const int64_t apitch = (int64_t)q.cpb * 48;             // code bytes per pixel
 
     // ---- epilogue vectors: no row terms (R = 0), the column constants with zw = 0
-    if (r.tid < BLK_BM) block_vectors(vtab, vtab + 3 * BLK_BM, r.tid, p, n, 0.0f, 0.0f);
+    if (!SPLIT && r.tid < BLK_BM) block_vectors(vtab, vtab + 3 * BLK_BM, r.tid, p, n, 0.0f, 0.0f);
 
     // ---- staging registers of one K tile: a block's 48 bytes are hi[0..15] | hi[16..23] lo[0..7] | lo[8..23]
     uint4 ra0, ra1, ra2;
@@ -90,11 +93,12 @@ __global__ __launch_bounds__(BLK_NT) void gemm_mxint8_kernel(GemmParams p, Block
 #pragma unroll
     for (int i = 0; i < 16; ++i) accf[0][0][i] = 0.0f;
     const int nkt = (q.nch + BLK_CH - 1) / BLK_CH;
-    load_tile(0);
-    for (int kt = 0; kt < nkt; ++kt) {
+    const int kt0 = SPLIT ? (int)blockIdx.z * z.tps : 0, kt1 = SPLIT ? min(kt0 + z.tps, nkt) : nkt;
+    load_tile(kt0);
+    for (int kt = kt0; kt < kt1; ++kt) {
         store_tile();
         __syncthreads();
-        if (kt + 1 < nkt) load_tile(kt + 1);
+        if (kt + 1 < kt1) load_tile(kt + 1);
 #pragma unroll
         for (int ii = 0; ii < BLK_CH / 4; ++ii) {
             const int pr = 2 * ii + r.wave_k;               // this K wave's chunk pairs of the tile
@@ -117,23 +121,53 @@ __global__ __launch_bounds__(BLK_NT) void gemm_mxint8_kernel(GemmParams p, Block
         }
         __syncthreads();
     }
-    block_store<TOut, MXI_RING>(p, smem, r, nkt, accf DGQ_DIAG_ARG);
+    if constexpr (SPLIT) block_store_partial(z, r, accf[0][0]);
+    else block_store<TOut, MXI_RING>(p, smem, r, nkt, accf DGQ_DIAG_ARG);
     DGQ_DIAG_FLUSH(mxint8, BLK_NW, r.wid, r.lane);
 }
 
-struct MxInt8Kernel { template <typename TOut> static constexpr auto fn = gemm_mxint8_kernel<TOut>; };
+template <typename TOut>
+__global__ __launch_bounds__(BLK_NT) void gemm_mxint8_kernel(GemmParams p, BlockGather q, MxInt8Operand o) {
+    gemm_mxint8_tile<TOut, false>(p, q, o, BlockSplit{});
+}
+__global__ __launch_bounds__(BLK_NT) void gemm_mxint8_split_kernel(GemmParams p, BlockGather q, MxInt8Operand o, BlockSplit z) {
+    gemm_mxint8_tile<float, true>(p, q, o, z);
+}
+
+struct MxInt8Kernel {
+    template <typename TOut> static constexpr auto fn = gemm_mxint8_kernel<TOut>;
+    static constexpr auto split = gemm_mxint8_split_kernel;
+};
 
 }  // namespace
 
-extern "C" int dgq_gemm_mxint8(const dgq_gemm_args_t* g, const dgq_gemm_mxint8_t* mx, void* stream) {
-    const char* who = "dgq_gemm_mxint8";
-    DGQ_CHECK_ARG(g && mx && mx->scale, "dgq_gemm_mxint8: null pointer");
+// what both entries do in front of their launch: the family's set-up and this format's operand
+static int gemm_mxint8_setup(const char* who, const dgq_gemm_args_t* g, const dgq_gemm_mxint8_t* mx, GemmParams& p, BlockGather& q, MxInt8Operand& o) {
+    DGQ_CHECK_ARG(g && mx && mx->scale, "%s: null pointer", who);
     const dgq_gemm_mxint8_t& k = *mx;
-    GemmParams p;
-    BlockGather q;
     const int rc = block_gemm_setup(who, *g, k.B, k.H, k.W, k.C, k.kh, k.kw, k.stride, k.pad, k.ups, false, p, q);
     if (rc != DGQ_OK) return rc;
-    DGQ_CHECK_ARG(k.lds >= q.cpb, "dgq_gemm_mxint8: scale pitch %d < %d blocks", k.lds, q.cpb);
-    const MxInt8Operand o = {k.scale, k.lds};
+    DGQ_CHECK_ARG(k.lds >= q.cpb, "%s: scale pitch %d < %d blocks", who, k.lds, q.cpb);
+    o = {k.scale, k.lds};
+    return DGQ_OK;
+}
+
+extern "C" int dgq_gemm_mxint8(const dgq_gemm_args_t* g, const dgq_gemm_mxint8_t* mx, void* stream) {
+    const char* who = "dgq_gemm_mxint8";
+    GemmParams p;
+    BlockGather q;
+    MxInt8Operand o;
+    const int rc = gemm_mxint8_setup(who, g, mx, p, q, o);
+    if (rc != DGQ_OK) return rc;
     return block_gemm_launch<MxInt8Kernel>(who, p, q, o, g->y_dtype, (hipStream_t)stream);
+}
+
+extern "C" int dgq_gemm_mxint8_splitk(const dgq_gemm_args_t* g, const dgq_gemm_mxint8_t* mx, int splits, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "dgq_gemm_mxint8_splitk";
+    GemmParams p;
+    BlockGather q;
+    MxInt8Operand o;
+    const int rc = gemm_mxint8_setup(who, g, mx, p, q, o);
+    if (rc != DGQ_OK) return rc;
+    return block_gemm_launch_split<MxInt8Kernel>(who, p, q, o, g->y_dtype, splits, workspace, workspace_bytes, (hipStream_t)stream);
 }

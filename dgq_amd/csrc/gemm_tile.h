@@ -197,6 +197,26 @@ __device__ __forceinline__ void gemm_clear_totals(v16i (&acc)[ACCS][TM][TN]) {
                 for (int r = 0; r < 16; ++r) acc[a][i][j][r] = ACC0;
 }
 
+// Sum of the split-K slabs of one 4-float segment, in slab order (the integer tile family's combine, gemm_wxa8.hip, and the block-scaled
+// family's, gemm_mx_split.hip).  R loads go out per round (a load per iteration of a
+// runtime-bounded loop is waited for before the next is issued: S dependent round trips); the launch picks R >= S where it can (one
+// round: the wide conv splits of the 8x8 / 16x16 levels have 8-16 slabs and spent 3-4 dependent rounds here).
+template <int R>
+__device__ __forceinline__ void splitk_sum_slabs(const float* base, int64_t slab_stride, int splits, float (&a)[4]) {
+    for (int s0 = 0; s0 < splits; s0 += R) {
+        float4 v[R];
+#pragma unroll
+        for (int j = 0; j < R; ++j) v[j] = *reinterpret_cast<const float4*>(base + (int64_t)min(s0 + j, splits - 1) * slab_stride);
+#pragma unroll
+        for (int j = 0; j < R; ++j)
+            if (s0 + j < splits) { a[0] += v[j].x; a[1] += v[j].y; a[2] += v[j].z; a[3] += v[j].w; }
+    }
+}
+__device__ __forceinline__ void splitk_sum(const float* base, int64_t slab_stride, int splits, float (&a)[4]) {
+    if (splits <= 4) splitk_sum_slabs<4>(base, slab_stride, splits, a);          // (uniform branches: splits is a kernel argument)
+    else if (splits <= 8) splitk_sum_slabs<8>(base, slab_stride, splits, a);
+    else splitk_sum_slabs<16>(base, slab_stride, splits, a);
+}
 
 // Store epilogue of one workgroup tile.  acc0 (per-M) / accf (per-K) hold the wave's (BM/WVM) x (BN/WVN) tile in the MFMA C/D
 // layout; vtab [3][BM] = R0 R1 R2 per row and vcol [4][BN] = alpha zw gamma vn per column were staged into LDS by the prologue;

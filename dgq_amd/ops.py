@@ -946,9 +946,10 @@ def _block_quant_launch(entry, x_cl, geom, bits, pre, ln, ups, pitch, outputs):
     return res
 
 
-def _block_gemm_launch(entry, k, q, geom, ab, out_dtype, out, extra, ups, **own):
+def _block_gemm_launch(entry, k, q, geom, ab, out_dtype, out, extra, ups, ksplit=1, **own):
     """One launch of a block GEMM entry on q = its quantiser's result (q[0]: the codes): the dgq_gemm_args_t of a block-mode layer —
-    ``own``: the fields the format adds — and the geometry of k, the format's struct carrying its own fields.  Returns y."""
+    ``own``: the fields the format adds — and the geometry of k, the format's struct carrying its own fields.  ksplit (the MX entries):
+    1 the entry itself; None (the plan's choice) or an int (forced): its ``_splitk`` form over workspace(device).  Returns y."""
     B, H, W, C, kh, kw, stride, pad = geom
     M = B * ((H + 2 * pad - kh) // stride + 1) * ((W + 2 * pad - kw) // stride + 1)
     pw = ab.pw
@@ -965,8 +966,15 @@ def _block_gemm_launch(entry, k, q, geom, ab, out_dtype, out, extra, ups, **own)
         g.extra = _c.cast(_c.pointer(extra), _c.c_void_p)
     k.B, k.H, k.W, k.C, k.kh, k.kw, k.stride, k.pad, k.ups = B, H, W, C, kh, kw, stride, pad, 1 if ups else 0
 
-    def issue(_keep=(q, out, extra, ab)):
-        _lib_call(entry, _c.byref(g), _c.byref(k), _lib.stream())
+    if ksplit == 1:
+        def issue(_keep=(q, out, extra, ab)):
+            _lib_call(entry, _c.byref(g), _c.byref(k), _lib.stream())
+    else:
+        ws = workspace(q[0].device)
+
+        def issue(_keep=(q, out, extra, ab, ws)):
+            _lib_call(entry + "_splitk", _c.byref(g), _c.byref(k), 0 if ksplit is None else int(ksplit), _c.c_void_p(ws.data_ptr()), ws.numel(),
+                      _lib.stream())
     issue()
     if BLOCK_LAUNCH_HOOK is not None:
         BLOCK_LAUNCH_HOOK(issue, "gemm", (M, pw.N, pw.K))
@@ -1027,12 +1035,13 @@ def dequant_act_mx6(codes, scale, out):
     return out
 
 
-def gemm_mx6(q, geom, ab: "MxActBinding", out_dtype, out=None, extra=None, ups=False):
+def gemm_mx6(q, geom, ab: "MxActBinding", out_dtype, out=None, extra=None, ups=False, ksplit=1):
     """One dgq_gemm_mx6 launch on q = quant_act_mx6(...) of the layer input; geom = (B, H, W, C, kh, kw, stride, pad) of the layer
-    (H, W: behind a folded upsample).  Returns y [M][N] (N/2 columns with the GEGLU epilogue)."""
+    (H, W: behind a folded upsample).  ksplit: 1 un-split; None the plan's K split (dgq_gemm_mx_plan_splits), an int a forced one —
+    dgq_gemm_mx6_splitk, the split launch and its combine over workspace(device).  Returns y [M][N] (N/2 columns with the GEGLU epilogue)."""
     k = _lib.GemmMx6()
     k.scale, k.lds = q[1].data_ptr(), q[1].shape[1]
-    return _block_gemm_launch("dgq_gemm_mx6", k, q, geom, ab, out_dtype, out, extra, ups, w_bits=4)
+    return _block_gemm_launch("dgq_gemm_mx6", k, q, geom, ab, out_dtype, out, extra, ups, ksplit=ksplit, w_bits=4)
 
 
 def quant_act_mxint8(x_cl: torch.Tensor, geom, pre=None, ln=None, ups=False, lds=None):
@@ -1055,11 +1064,11 @@ def dequant_act_mxint8(codes, scale, out):
     return out
 
 
-def gemm_mxint8(q, geom, ab: "MxActBinding", out_dtype, out=None, extra=None, ups=False):
-    """One dgq_gemm_mxint8 launch on q = quant_act_mxint8(...) of the layer input; geom and the result as for gemm_mx6."""
+def gemm_mxint8(q, geom, ab: "MxActBinding", out_dtype, out=None, extra=None, ups=False, ksplit=1):
+    """One dgq_gemm_mxint8 launch on q = quant_act_mxint8(...) of the layer input; geom, ksplit and the result as for gemm_mx6."""
     k = _lib.GemmMxInt8()
     k.scale, k.lds = q[1].data_ptr(), q[1].shape[1]
-    return _block_gemm_launch("dgq_gemm_mxint8", k, q, geom, ab, out_dtype, out, extra, ups, w_bits=4)
+    return _block_gemm_launch("dgq_gemm_mxint8", k, q, geom, ab, out_dtype, out, extra, ups, ksplit=ksplit, w_bits=4)
 
 
 def _block_quant(ab, x_cl, geom, pre=None, ln=None, ups=False, pad_k=False):
@@ -1069,9 +1078,21 @@ def _block_quant(ab, x_cl, geom, pre=None, ln=None, ups=False, pad_k=False):
     return quant_act_block(x_cl, geom, ab.abits, pre, ln, ups, ldt=ab.Kp // 32 if pad_k else None)
 
 
+#: the K split of the MX layers (quant_linear, quant_conv2d, the batched Linear path): None = the library's plan per shape
+#: (dgq_gemm_mx_plan_splits), 1 = never, an int = forced — what _block_gemm hands to gemm_mx6 / gemm_mxint8 as ``ksplit``
+MX_KSPLIT = None
+
+
 def _block_gemm(ab, q, geom, out_dtype, out=None, extra=None, ups=False):
-    gemm = (gemm_mxint8 if ab.fmt == "mxint8" else gemm_mx6) if ab.mx else gemm_blockq
-    return gemm(q, geom, ab, out_dtype, out=out, extra=extra, ups=ups)
+    if not ab.mx:
+        return gemm_blockq(q, geom, ab, out_dtype, out=out, extra=extra, ups=ups)
+    ksplit = MX_KSPLIT
+    if ksplit is None:                                      # the plan says un-split: the un-split entry, and no workspace is asked for
+        B, H, W, C, kh, kw, stride, pad = geom
+        M = B * ((H + 2 * pad - kh) // stride + 1) * ((W + 2 * pad - kw) // stride + 1)
+        if _lib.load().dgq_gemm_mx_plan_splits(M, ab.pw.N, ab.Kp, WORKSPACE_BYTES) == 1:
+            ksplit = 1
+    return (gemm_mxint8 if ab.fmt == "mxint8" else gemm_mx6)(q, geom, ab, out_dtype, out=out, extra=extra, ups=ups, ksplit=ksplit)
 
 
 def quant_linear(x: torch.Tensor, ab: ActBinding, pre_act=0, residual=None, fq=None, ln=None, geglu=False):

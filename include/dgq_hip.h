@@ -500,6 +500,20 @@ typedef struct dgq_gemm_mxint8 {
     int B, H, W, C, kh, kw, stride, pad, ups;
 } dgq_gemm_mxint8_t;
 int dgq_gemm_mxint8(const dgq_gemm_args_t* g, const dgq_gemm_mxint8_t* mx, void* stream);
+/* ---- the K split of the two block-scaled GEMMs (the long-K, low-M layers: few 64 x 64 tiles, each a long serial walk of K) -------------
+ * dgq_gemm_mx6_splitk / dgq_gemm_mxint8_splitk: the same layer as dgq_gemm_mx6 / dgq_gemm_mxint8 (same arguments, same checks, same
+ * epilogue forms) in TWO launches: S workgroups per tile each walk 1/S of the K tiles (of 256) and leave their raw fp32 accumulators in
+ * `workspace` (32 KiB per tile and split; 16-byte aligned, else DGQ_EINVAL), then one combine kernel adds a tile's partials in a fixed
+ * order (split 0 .. S − 1 inside each of the tile's two K waves, then the two K waves as un-split) and runs the store epilogue.  No
+ * atomics, no counters: deterministic, capture-safe, and different from the un-split result only in fp32 summation order.  splits = 0:
+ * the plan's S; splits >= 1: forced.  Either is clamped to the K tiles and to what workspace_bytes holds (workspace NULL or too small
+ * lowers S, down to 1); S = 1 is the un-split kernel in one launch.
+ * dgq_gemm_mx_plan_splits: the S the plan takes for a shape and a workspace of that size (1: un-split); dgq_gemm_mx_workspace_bytes: what
+ * the plan's preferred S of a shape needs (0: un-split). */
+int dgq_gemm_mx6_splitk(const dgq_gemm_args_t* g, const dgq_gemm_mx6_t* mx, int splits, void* workspace, size_t workspace_bytes, void* stream);
+int dgq_gemm_mxint8_splitk(const dgq_gemm_args_t* g, const dgq_gemm_mxint8_t* mx, int splits, void* workspace, size_t workspace_bytes, void* stream);
+int dgq_gemm_mx_plan_splits(int M, int N, int Kp, size_t workspace_bytes);
+size_t dgq_gemm_mx_workspace_bytes(int M, int N, int Kp);
 /* Small tile grids are split along K (deterministic: fp32 partial slabs [S][M][N] in the caller's `workspace`,
  * summed in a fixed order by a second kernel). dgq_gemm_workspace_bytes returns what the preferred split of a
  * shape needs; with workspace == NULL (or too small) fewer / no splits are used — results do not depend on it

@@ -182,6 +182,55 @@ def mx_kernel_table(torch, ops, dev, lines, fmt="mxfp6"):
     lines.append("shapes where the MX pair is slower than the block pair: %s" % (", ".join(slower) if slower else "none"))
 
 
+#: the rows of mx_kernel_table, the SD 8x8 / 16x16 convolutions not among them, and the two 9-K-tile shapes of the tests (tiny UNet, route test)
+KSPLIT_SHAPES = [("linear 8192x320 -> 320", (8192, 1, 1, 320, 1, 1, 1, 0), 320, False), ("linear 8192x320 -> 2560", (8192, 1, 1, 320, 1, 1, 1, 0), 2560, False),
+                 ("linear 8192x1280 -> 320", (8192, 1, 1, 1280, 1, 1, 1, 0), 320, False), ("linear 2048x640 -> 640", (2048, 1, 1, 640, 1, 1, 1, 0), 640, False),
+                 ("linear 2048x2560 -> 640", (2048, 1, 1, 2560, 1, 1, 1, 0), 640, False), ("linear 512x1280 -> 1280", (512, 1, 1, 1280, 1, 1, 1, 0), 1280, False),
+                 ("linear 154x768 -> 320", (154, 1, 1, 768, 1, 1, 1, 0), 320, False),
+                 ("conv3x3 2x320x64x64 -> 320", (2, 64, 64, 320, 3, 3, 1, 1), 320, False), ("conv3x3 s2 2x320x64x64 -> 320", (2, 64, 64, 320, 3, 3, 2, 1), 320, False),
+                 ("conv3x3 2x640x32x32 -> 640", (2, 32, 32, 640, 3, 3, 1, 1), 640, False), ("conv3x3 2x1280x32x32 -> 640", (2, 32, 32, 1280, 3, 3, 1, 1), 640, False),
+                 ("conv3x3 2x1280x16x16 -> 1280", (2, 16, 16, 1280, 3, 3, 1, 1), 1280, False), ("conv3x3 2x2560x8x8 -> 1280", (2, 8, 8, 2560, 3, 3, 1, 1), 1280, False),
+                 ("conv3x3 2x1280x8x8 -> 1280", (2, 8, 8, 1280, 3, 3, 1, 1), 1280, False), ("conv3x3 2x2560x16x16 -> 1280", (2, 16, 16, 2560, 3, 3, 1, 1), 1280, False),
+                 ("conv3x3 2x1920x16x16 -> 1280", (2, 16, 16, 1920, 3, 3, 1, 1), 1280, False), ("conv3x3 ups 2x1280x8x8 -> 1280", (2, 16, 16, 1280, 3, 3, 1, 1), 1280, True),
+                 ("conv3x3 s2 2x640x32x32 -> 640", (2, 32, 32, 640, 3, 3, 2, 1), 640, False), ("conv3x3 s2 2x1280x16x16 -> 1280", (2, 16, 16, 1280, 3, 3, 2, 1), 1280, False),
+                 ("conv3x3 2x256x8x8 -> 128 (tiny)", (2, 8, 8, 256, 3, 3, 1, 1), 128, False), ("conv3x3 2x256x4x4 -> 64 (test)", (2, 4, 4, 256, 3, 3, 1, 1), 64, False)]
+
+
+def mx_ksplit_table(torch, ops, dev, lines, fmt, sweep=(2, 4, 8, 16)):
+    """the MX GEMM of ``fmt`` per shape: un-split (captured twice: the spread of its own medians), forced K splits, and the plan's route —
+    the split figures are the PAIR of launches (GEMM + combine); alternating rounds of hipGraph replays"""
+    from dgq_amd import _lib, synth
+    quant_mx, gemm_mx = (ops.quant_act_mxint8, ops.gemm_mxint8) if fmt == "mxint8" else (ops.quant_act_mx6, ops.gemm_mx6)
+    lines += ["", "%s GEMM alone per shape (fp32 out; 20 calls per hipGraph replay, median of 7 ALTERNATING rounds): un-split twice (S=1, S=1'),"
+              % fmt.upper(), "forced splits (GEMM + combine), the plan's route; tiles = 64x64 output tiles, nkt = K tiles of 256; MB = the plan's workspace",
+              "%-34s %6s %4s %8s %8s %s %5s %8s %7s" % ("layer", "tiles", "nkt", "S=1 us", "S=1' us", " ".join("%8s" % ("S=%d us" % s) for s in sweep), "plan", "plan us", "MB")]
+    g = torch.Generator().manual_seed(0)
+    lib, worst_ws = _lib.load(), 0
+    for name, geom, N, ups in KSPLIT_SHAPES:
+        B, H, W, C, kh, kw, stride, pad = geom
+        taps = kh * kw
+        w = torch.randn(N, C * taps, generator=g) * (C * taps) ** -0.5
+        wd, wz = synth.channel_minmax(w, 4)
+        mxb = ops.MxActBinding(ops.PackedWeight(w.to(dev), wd.to(dev), wz.to(dev), None, torch.zeros(N).to(dev), 4, C, taps), fmt)
+        sh = 1 if ups else 0
+        x = (torch.randn(B, H >> sh, W >> sh, C, generator=g) * 1.3 + 0.2).to(dev)
+        qm = quant_mx(x, geom, ups=ups, lds=mxb.Kp // 32 if taps == 1 else C // 32)
+        M = B * ((H + 2 * pad - kh) // stride + 1) * ((W + 2 * pad - kw) // stride + 1)
+        tiles, nkt = ((M + 63) // 64) * ((N + 63) // 64), (C * taps // 32 + 7) // 8
+        call = lambda s: captured(torch, lambda: gemm_mx(qm, geom, mxb, torch.float32, ups=ups, ksplit=s))
+        plan = lib.dgq_gemm_mx_plan_splits(M, N, mxb.Kp, ops.WORKSPACE_BYTES)
+        graphs = {"a": call(1), "b": call(1)}
+        graphs.update({s: call(s) for s in sweep if s <= nkt})
+        graphs["plan"] = call(1 if plan == 1 else None)
+        us = alternating_us(torch, graphs)
+        ws = lib.dgq_gemm_mx_workspace_bytes(M, N, mxb.Kp)
+        worst_ws = max(worst_ws, ws)
+        lines.append("%-34s %6d %4d %8.2f %8.2f %s %5d %8.2f %7.1f" % (name, tiles, nkt, us["a"], us["b"], " ".join("%8.2f" % us[s] if s in us else "%8s" % "-" for s in sweep),
+                                                                  plan, us["plan"], ws / 2 ** 20))
+        del graphs
+    lines.append("largest plan workspace over these shapes: %.1f MB of ops.WORKSPACE_BYTES = %d MB" % (worst_ws / 2 ** 20, ops.WORKSPACE_BYTES >> 20))
+
+
 def build_rt_model(torch, arch, fmt, abits, steps_cfg, batch, res, dev, use_aq=True):
     """a real-time model of ``arch`` from a weight-only checkpoint at W4 / ``abits``: fmt "row", "block" or "mxfp6"; use_aq False: the
     weight-only state (un-quantised activations)"""
@@ -226,7 +275,8 @@ def mx_step_table(torch, ops, args, dev, lines, modes=MX_MODES, ab=6):
     ctx = synth.named_randn("ctx", (2, 77, 768), 100).to(dev)
     models, info = {}, {}
     for mode, _label in modes:
-        qnn = build_rt_model(torch, "sd", mode, ab, 50, 2, 64, dev)
+        ops.MX_KSPLIT = 1 if mode.endswith("@1") else None     # "<fmt>@1": the MX mode captured with its K split off (the plan is read at capture)
+        qnn = build_rt_model(torch, "sd", mode.split("@")[0], ab, 50, 2, 64, dev)
 
         def one_step(x, t, qnn=qnn):
             eps = qnn(torch.cat([x, x], dim=0), t, ctx)[0]
@@ -246,6 +296,7 @@ def mx_step_table(torch, ops, args, dev, lines, modes=MX_MODES, ab=6):
         for c in calls:
             by[c] = by.get(c, 0) + 1
         models[mode], info[mode] = one_step, (len(calls), by, [])
+    ops.MX_KSPLIT = None
     with torch.no_grad():
         for _ in range(args.windows):
             for mode, _label in modes:
@@ -262,6 +313,7 @@ def mx_step_table(torch, ops, args, dev, lines, modes=MX_MODES, ab=6):
     lines += ["", "SD1.4-size synthetic model, 512^2 (64x64 latents), CFG pair, fp32, W4A%d, weight-only checkpoint; hipGraph replay, %d timed steps behind"
               % (ab, args.steps), "%d warm-up steps per window, %d ALTERNATING rounds (rows, blocks, MX blocks, rows, ...) in one process on one box" % (args.warmup, args.windows),
               "%-44s %10s %10s %10s %12s" % ("mode", "median ms", "min ms", "max ms", "entry calls")]
+    args.rounds_log = [info[mode][2] for mode, _ in modes]     # per mode, the rounds in order
     for mode, label in modes:
         ncalls, by, ms = info[mode]
         lines.append("%-44s %10.3f %10.3f %10.3f %12d" % (label, statistics.median(ms), min(ms), max(ms), ncalls))
@@ -432,6 +484,7 @@ def main(argv=None):
     ap.add_argument("--block", action="store_true", help="measure the real-time block mode (see the head of this file)")
     ap.add_argument("--mx", action="store_true", help="measure the real-time MXFP6 mode (see the head of this file)")
     ap.add_argument("--mxint8", action="store_true", help="measure the real-time MXINT8 mode (see the head of this file)")
+    ap.add_argument("--mx-ksplit", action="store_true", help="measure the K split of the two MX GEMMs: per shape, and (without --kernels-only) per step")
     ap.add_argument("--append", default=None, help="--mx / --mxint8: a text file whose lines are appended to the report (the tests' measured constants)")
     args = ap.parse_args(argv)
     import torch
@@ -440,6 +493,27 @@ def main(argv=None):
     _lib.require_gpu()
     torch.set_num_threads(min(torch.get_num_threads(), 16))
     dev = torch.device("cuda", 0)
+    if args.mx_ksplit:
+        lines = ["K split of the block-scaled MX GEMMs (dgq_gemm_mx6_splitk / dgq_gemm_mxint8_splitk) — tools/profile_realtime_act.py --mx-ksplit",
+                 "commit %s; %s; torch %s; ABI %d" % (args.stamp or stamp_default(), torch.cuda.get_device_name(0), torch.__version__, _lib.ABI_VERSION)]
+        for fmt in ("mxfp6", "mxint8"):
+            mx_ksplit_table(torch, ops, dev, lines, fmt)
+        if not args.kernels_only:
+            for fmt, ab in (("mxfp6", 6), ("mxint8", 8)):
+                mx_step_table(torch, ops, args, dev, lines, (("row", "real-time rows, A%d" % ab), (fmt + "@1", "real-time %s blocks, un-split" % fmt.upper()),
+                                                             (fmt, "real-time %s blocks, the plan's K split" % fmt.upper())), ab)
+                lines.append("per round (ms), un-split | split: " + "; ".join("%.3f | %.3f" % p for p in zip(args.rounds_log[-2], args.rounds_log[-1])))
+                ops._WORKSPACE.clear()
+                gc.collect()
+                torch.cuda.empty_cache()
+        if args.append:
+            lines += [""] + open(args.append).read().splitlines()
+        text = "\n".join(lines) + "\n"
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text)
+        print(text)
+        return 0
     if args.mx or args.mxint8:
         fmt, modes, ab = ("mxint8", MXINT8_MODES, 8) if args.mxint8 else ("mxfp6", MX_MODES, 6)
         lines = ["real-time %s activation mode (real_time_format=\"%s\", W4A%d) — tools/profile_realtime_act.py --%s"
