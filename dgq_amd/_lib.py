@@ -64,6 +64,9 @@ SIGNATURES = {
     "dgq_gemm_mx6_splitk": [_vp, _vp, _i, _vp, ctypes.c_size_t, _vp],
     "dgq_gemm_mxint8_splitk": [_vp, _vp, _i, _vp, ctypes.c_size_t, _vp],
     "dgq_gemm_mx_plan_splits": [_i, _i, _i, ctypes.c_size_t],
+    "dgq_pack_w_mx6x2": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "dgq_gemm_mxw8": [_vp, _vp, _vp],
+    "dgq_gemm_mxw8_splitk": [_vp, _vp, _i, _vp, ctypes.c_size_t, _vp],
     "dgq_gemm_mx_workspace_bytes": [_i, _i, _i],
     "dgq_gemm_wxa8_batch": [_i, _vp, _vp],
     "dgq_adaround_soft_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
@@ -146,6 +149,11 @@ class ActMxInt8Out(ctypes.Structure):
 class GemmMxInt8(ctypes.Structure):
     """dgq_gemm_mxint8_t of include/dgq_hip.h"""
     _fields_ = GemmMx6._fields_
+
+
+class GemmMxW8(ctypes.Structure):
+    """dgq_gemm_mxw8_t of include/dgq_hip.h"""
+    _fields_ = GemmMx6._fields_ + [("a_format", _i)]
 
 
 class GemmArgs(ctypes.Structure):

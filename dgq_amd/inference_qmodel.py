@@ -56,6 +56,9 @@ def parse_args(argv=None):
                         "32 FP6 E2M3 codes on the block-scaled matrix cores (dgq_quant_act_mx6 + dgq_gemm_mx6; W4 layers, W4A6); with 8 "
                         "activation bits: mxint8 = every block one power-of-two scale and 32 int8 codes, run as two E2M3 terms on the same "
                         "cores (dgq_quant_act_mxint8 + dgq_gemm_mxint8; W4 layers, W4A8)")
+    p.add_argument("--aq_real_time_mx_w8", action="store_true",
+                   help="with --aq_real_time_format mxfp6 / mxint8: W8 layers (integer zero points) take the MX format too, their weight "
+                        "as two FP6 E2M3 planes (dgq_pack_w_mx6x2 + dgq_gemm_mxw8; W8A6 / W8A8) instead of the int8 block mode")
     p.add_argument("--wq_mfma16", action="store_true",
                    help="weight-only state (no --use_aq): run the layers on the bf16 / f16 matrix cores (dgq_conv2d_wq_mfma16) — faster, "
                         "not bit-identical to the default exact route")
@@ -98,6 +101,8 @@ def main(argv=None):
     if opt.aq_real_time_format == "mxint8" and not (opt.use_aq and opt.aq_real_time and opt.aq_real_time_block == 32 and opt.aq == 8):
         raise SystemExit("--aq_real_time_format mxint8 is a format of the real-time block mode at 8 activation bits: it needs --use_aq "
                          "--aq_real_time --aq_real_time_block 32 and --aq 8")
+    if opt.aq_real_time_mx_w8 and opt.aq_real_time_format not in ("mxfp6", "mxint8"):
+        raise SystemExit("--aq_real_time_mx_w8 extends an MX format to the W8 layers: it needs --aq_real_time_format mxfp6 or mxint8")
     logging.basicConfig(level=logging.INFO)
     from .diffusers_rewrite import UNet2DConditionModel, ARCH
     from .quant import get_qmodel, Scaler
@@ -143,6 +148,8 @@ def main(argv=None):
             aq_params["real_time_block"] = opt.aq_real_time_block
         if opt.aq_real_time_format != "int":
             aq_params["real_time_format"] = opt.aq_real_time_format
+        if opt.aq_real_time_mx_w8:
+            aq_params["real_time_mx_w8"] = True
     softmax_aq_params = {"softmax_a_bit": opt.aq, "t2i_log_quant": opt.t2i_log_quant,
                          "t2i_real_time": opt.t2i_real_time, "t2i_start_peak": opt.t2i_start_peak, "log_max_1": False}
     time_aware = opt.time_aware_aqtizer if opt.use_aq else False

@@ -163,6 +163,8 @@ class PackedWeight:
         self._mfma16 = None
         self._mx6 = None
         self._mx6_ok = None
+        self._mx6x2 = None
+        self._mxw8_ok = None
 
     @property
     def mx6_eligible(self):
@@ -182,6 +184,25 @@ class PackedWeight:
             _lib_call("dgq_pack_w_mx6", _lib.ptr(self.codes), _lib.ptr(self.zp_true), self.N, self.C, self.taps, Kp, _lib.ptr(img), _lib.stream())
             self._mx6 = (img, Kp)
         return self._mx6
+
+    @property
+    def mxw8_eligible(self):
+        """True when dgq_gemm_mxw8 may take this weight: W8, integer zero points and |q − z| <= 255 (the arithmetic of check_mfma16), so
+        that q − z splits into two FP6 E2M3 planes (quant_layer.mxw8_split).  Computed once per packed weight."""
+        if self._mxw8_ok is None:
+            self._mxw8_ok = self.bits == 8 and self.check_mfma16(self.codes, self.zp_true, 8)
+        return self._mxw8_ok
+
+    def mx6x2(self):
+        """(image, Kp): the two E2M3 planes of q − z in the natural K order, [N][Kp/32][48] bytes = H plane | L plane per block
+        (dgq_pack_w_mx6x2) — cached, one extra image per layer at 1.5 bytes per weight"""
+        if self._mx6x2 is None:
+            assert self.mxw8_eligible, "PackedWeight.mx6x2: W8 with integer zero points and |q - z| <= 255"
+            Kp = round_up(self.K, KTILE)
+            img = torch.empty((self.N, Kp // 32, 48), dtype=torch.uint8, device=self.codes.device)
+            _lib_call("dgq_pack_w_mx6x2", _lib.ptr(self.codes), _lib.ptr(self.zp_true), self.N, self.C, self.taps, Kp, _lib.ptr(img), _lib.stream())
+            self._mx6x2 = (img, Kp)
+        return self._mx6x2
 
     def mfma16_eligible(self):
         """True when dgq_conv2d_wq_mfma16 may take this weight: the zero points are integers and every q − z fits the bound (15 for
@@ -395,19 +416,21 @@ class MxActBinding(BlockActBinding):
     real_time_format="mxfp6")) on a layer whose weight is exact in FP6 E2M3 (PackedWeight.mx6_eligible): the MX weight image, bias and δw —
     no tables, no timestep slots, one binding per layer.  The routes of a block binding run it as dgq_quant_act_mx6 on the layer INPUT
     (once per row / pixel: 24 code bytes and one E8M0 scale byte per 32-channel block) + dgq_gemm_mx6.  ``fmt`` carries the MX format:
-    real_time_format="mxint8" (8 bits) is the same binding on the MXINT8 entries."""
+    real_time_format="mxint8" (8 bits) is the same binding on the MXINT8 entries.  ``w_bits=8`` (real_time_mx_w8=True on a W8 layer,
+    PackedWeight.mxw8_eligible) binds the two-plane W8 image instead: the same quantisers + dgq_gemm_mxw8."""
 
     mx = True
 
-    def __init__(self, pw: PackedWeight, fmt: str = "mxfp6"):
+    def __init__(self, pw: PackedWeight, fmt: str = "mxfp6", *, w_bits: int = 4):
         """fmt "mxint8" (real_time_format="mxint8", 8 bits): the same weight image and eligibility under MXINT8 blocks — 48 code bytes
-        (two E2M3 planes of the int8 code) and one scale byte per block, dgq_quant_act_mxint8 + dgq_gemm_mxint8"""
+        (two E2M3 planes of the int8 code) and one scale byte per block, dgq_quant_act_mxint8 + dgq_gemm_mxint8.  w_bits 8: the image of
+        PackedWeight.mx6x2 under either format (dgq_gemm_mxw8)"""
         assert pw.C % 32 == 0, "real-time MX quantizer: C % 32 == 0"
-        assert fmt in ("mxfp6", "mxint8")
-        self.fmt = fmt
+        assert fmt in ("mxfp6", "mxint8") and w_bits in (4, 8)
+        self.fmt, self.w_bits = fmt, w_bits
         self.mode, self.abits, self.offset = "block", 8 if fmt == "mxint8" else 6, 0.0
         self.pw = pw
-        self.wpacked, self.Kp = pw.mx6()
+        self.wpacked, self.Kp = pw.mx6x2() if w_bits == 8 else pw.mx6()
         self.wfrag = None
         self.ksrc = None
         self._koff = {}
@@ -1071,6 +1094,14 @@ def gemm_mxint8(q, geom, ab: "MxActBinding", out_dtype, out=None, extra=None, up
     return _block_gemm_launch("dgq_gemm_mxint8", k, q, geom, ab, out_dtype, out, extra, ups, ksplit=ksplit, w_bits=4)
 
 
+def gemm_mxw8(q, geom, ab: "MxActBinding", out_dtype, out=None, extra=None, ups=False, ksplit=1):
+    """One dgq_gemm_mxw8 launch on q = quant_act_mx6(...) or quant_act_mxint8(...) (ab.fmt) of the layer input against the two-plane W8
+    image of ab (MxActBinding(pw, fmt, w_bits=8)); geom, ksplit and the result as for gemm_mx6."""
+    k = _lib.GemmMxW8()
+    k.scale, k.lds, k.a_format = q[1].data_ptr(), q[1].shape[1], ab.abits
+    return _block_gemm_launch("dgq_gemm_mxw8", k, q, geom, ab, out_dtype, out, extra, ups, ksplit=ksplit, w_bits=8)
+
+
 def _block_quant(ab, x_cl, geom, pre=None, ln=None, ups=False, pad_k=False):
     """the input of a block binding quantised by its format's entry; pad_k: table / scale entries up to Kp/32 (Linear layers)"""
     if ab.mx:
@@ -1079,7 +1110,7 @@ def _block_quant(ab, x_cl, geom, pre=None, ln=None, ups=False, pad_k=False):
 
 
 #: the K split of the MX layers (quant_linear, quant_conv2d, the batched Linear path): None = the library's plan per shape
-#: (dgq_gemm_mx_plan_splits), 1 = never, an int = forced — what _block_gemm hands to gemm_mx6 / gemm_mxint8 as ``ksplit``
+#: (dgq_gemm_mx_plan_splits), 1 = never, an int = forced — what _block_gemm hands to gemm_mx6 / gemm_mxint8 / gemm_mxw8 as ``ksplit``
 MX_KSPLIT = None
 
 
@@ -1092,7 +1123,8 @@ def _block_gemm(ab, q, geom, out_dtype, out=None, extra=None, ups=False):
         M = B * ((H + 2 * pad - kh) // stride + 1) * ((W + 2 * pad - kw) // stride + 1)
         if _lib.load().dgq_gemm_mx_plan_splits(M, ab.pw.N, ab.Kp, WORKSPACE_BYTES) == 1:
             ksplit = 1
-    return (gemm_mxint8 if ab.fmt == "mxint8" else gemm_mx6)(q, geom, ab, out_dtype, out=out, extra=extra, ups=ups, ksplit=ksplit)
+    gemm = gemm_mxw8 if ab.w_bits == 8 else gemm_mxint8 if ab.fmt == "mxint8" else gemm_mx6
+    return gemm(q, geom, ab, out_dtype, out=out, extra=extra, ups=ups, ksplit=ksplit)
 
 
 def quant_linear(x: torch.Tensor, ab: ActBinding, pre_act=0, residual=None, fq=None, ln=None, geglu=False):

@@ -258,6 +258,22 @@ def mxint8_split(codes: torch.Tensor):
     return hi.to(torch.uint8), code[l.long()].to(torch.uint8)
 
 
+def mxw8_split(d: torch.Tensor):
+    """The two E2M3 code planes of centred W8 weights d = q − z (integers, |d| <= 255): with H = |d| >> 4 and L = |d| & 15,
+    d = sign(d)·(16·H + L) = 32·(±H/2) + 2·(±L/2), and H/2, L/2 are E2M3 grid values (the sign-magnitude split: two's complement would
+    need h = −16, and −8 is not on the grid).  Returns (hi6, lo6) uint8 6-bit codes of the shape of ``d``: sign << 5 | magnitude code
+    of H/2 resp. L/2, a zero magnitude stored +0.  ``mx6_pack`` packs each plane; dgq_pack_w_mx6x2 writes both."""
+    v = d.to(torch.int32)
+    a = v.abs()
+    assert int(a.max()) <= 255 if a.numel() else True
+    code = torch.tensor([E2M3_MAGNITUDES.index(n / 2.0) for n in range(16)], dtype=torch.int32, device=v.device)
+    H, L = a >> 4, a & 15
+    sign = torch.where(v < 0, 32, 0).to(torch.int32)
+    hi = code[H.long()] | torch.where(H > 0, sign, torch.zeros_like(sign))
+    lo = code[L.long()] | torch.where(L > 0, sign, torch.zeros_like(sign))
+    return hi.to(torch.uint8), lo.to(torch.uint8)
+
+
 def group_params_from_ranges(in_min, in_max, out_min, out_max, group_num, mode, level, force_in_channel=None):
     """The host half of ``done_group_num`` (quant_layer.py:338-418) as a pure function of the folded range vectors —
     returns (δ, z, in_channel_wise) in the checkpoint's broadcast shapes.  Arithmetic follows the reference line by
@@ -323,11 +339,16 @@ class UniformAffineQuantizer(nn.Module):
     ``real_time_format="mxint8"`` (with ``real_time_block=32`` and 8 bits): the block is an OCP MXINT8 block — one power-of-two scale
     and 32 int8 codes (``mxint8_block``), each split exactly into two E2M3 terms (``mxint8_split``) for the same matrix cores
     (dgq_quant_act_mxint8 + dgq_gemm_mxint8).  The same layers take it as take MXFP6; every other layer runs as with
+    ``real_time_block=32`` alone.
+
+    ``real_time_mx_w8=True`` (with either MX format; opt-in): W8 layers with integer zero points and C % 32 == 0 take the MX format too,
+    their weight as two E2M3 planes (``mxw8_split``; dgq_pack_w_mx6x2 + dgq_gemm_mxw8) — without it they run as with
     ``real_time_block=32`` alone."""
 
     def __init__(self, bits: int = 8, symmetric: bool = False, channel_wise: bool = False,
                  scaler: Scaler = Scaler.MINMAX, leaf_param: bool = False, always_zero: bool = False,
-                 quant_emb: bool = False, real_time: bool = False, real_time_block: int = 0, real_time_format: str = "int") -> None:
+                 quant_emb: bool = False, real_time: bool = False, real_time_block: int = 0, real_time_format: str = "int",
+                 real_time_mx_w8: bool = False) -> None:
         super().__init__()
         if symmetric:
             raise NotImplementedError("symmetric quantizers are not used by the DGQ inference path")
@@ -342,6 +363,9 @@ class UniformAffineQuantizer(nn.Module):
             raise ValueError("real_time_format=\"mxfp6\" is a format of real_time=True with real_time_block=%d and bits=6" % REAL_TIME_BLOCK)
         if real_time_format == "mxint8" and not (real_time and real_time_block == REAL_TIME_BLOCK and bits == 8):
             raise ValueError("real_time_format=\"mxint8\" is a format of real_time=True with real_time_block=%d and bits=8" % REAL_TIME_BLOCK)
+        if real_time_mx_w8 and real_time_format not in ("mxfp6", "mxint8"):
+            raise ValueError("real_time_mx_w8=True extends real_time_format=\"mxfp6\" / \"mxint8\" to W8 layers: it needs one of them")
+        self.real_time_mx_w8 = bool(real_time_mx_w8)
         self.real_time = bool(real_time)
         self.real_time_block = int(real_time_block)
         self.real_time_format = real_time_format
@@ -522,7 +546,8 @@ class UniformAffineQuantizer(nn.Module):
         return "level=%d, channel_wise=%s, leaf_param=%s, always_zero=%s%s" % (
             self.level, self.channel_wise, self.leaf_param, self.always_zero,
             (", real_time=True" + (", real_time_block=%d" % self.real_time_block if self.real_time_block else "")
-             + (", real_time_format=%s" % self.real_time_format if self.real_time_format != "int" else "")) if self.real_time else "")
+             + (", real_time_format=%s" % self.real_time_format if self.real_time_format != "int" else "")
+             + (", real_time_mx_w8=True" if self.real_time_mx_w8 else "")) if self.real_time else "")
 
     def half(self):
         super().half()
@@ -728,13 +753,17 @@ class QuantLayer(nn.Module):
         if self.aqtizer.real_time:                # no tables, no slots: one natural-order binding, its row tables made per call
             if "real_time" not in self._bindings:
                 # block granularity where the input channels split into whole 32-blocks; the per-row mode otherwise
-                # (MXFP6 / MXINT8 blocks where the format asks for them and the weight is exact in E2M3)
+                # (MXFP6 / MXINT8 blocks where the format asks for them and the weight is exact in E2M3 — W4 in one plane; with
+                # real_time_mx_w8, W8 in two)
                 blk = self.aqtizer.real_time_block
                 whole = blk and self.in_channels % blk == 0
-                if whole and self.aqtizer.real_time_format == "mxfp6" and pw.mx6_eligible:
+                fmt = self.aqtizer.real_time_format
+                if whole and fmt == "mxfp6" and pw.mx6_eligible:
                     self._bindings["real_time"] = ops.MxActBinding(pw)
-                elif whole and self.aqtizer.real_time_format == "mxint8" and pw.mx6_eligible:
+                elif whole and fmt == "mxint8" and pw.mx6_eligible:
                     self._bindings["real_time"] = ops.MxActBinding(pw, "mxint8")
+                elif whole and self.aqtizer.real_time_mx_w8 and pw.bits == 8 and pw.mxw8_eligible:
+                    self._bindings["real_time"] = ops.MxActBinding(pw, fmt, w_bits=8)
                 else:
                     self._bindings["real_time"] = (ops.BlockActBinding(pw, self.aqtizer.bits) if whole
                                                    else ops.DynamicActBinding(pw, self.aqtizer.bits))

@@ -51,7 +51,9 @@ extern "C" {
  *        dgq_quant_act_mx6 / dgq_dequant_act_mx6 / dgq_pack_w_mx6 / dgq_gemm_mx6 with dgq_act_mx6_out_t and dgq_gemm_mx6_t;
  *        dgq_conv2d_wq_mfma16_fused with its dgq_wq16_fuse_t — norms, SiLU, GEGLU and the residual folded into the weight-only
  *        matrix-core layer — and dgq_layernorm_row_stats; the real-time MXINT8 mode, dgq_quant_act_mxint8 / dgq_dequant_act_mxint8 /
- *        dgq_gemm_mxint8 with dgq_act_mxint8_out_t and dgq_gemm_mxint8_t */
+ *        dgq_gemm_mxint8 with dgq_act_mxint8_out_t and dgq_gemm_mxint8_t; their K split (dgq_gemm_mx6_splitk, dgq_gemm_mxint8_splitk,
+ *        dgq_gemm_mx_plan_splits, dgq_gemm_mx_workspace_bytes); W8 weights under both MX formats, dgq_pack_w_mx6x2 / dgq_gemm_mxw8 /
+ *        dgq_gemm_mxw8_splitk with dgq_gemm_mxw8_t */
 #define DGQ_ABI_VERSION 123
 int dgq_version(void);
 const char* dgq_last_error(void);
@@ -514,6 +516,28 @@ int dgq_gemm_mx6_splitk(const dgq_gemm_args_t* g, const dgq_gemm_mx6_t* mx, int 
 int dgq_gemm_mxint8_splitk(const dgq_gemm_args_t* g, const dgq_gemm_mxint8_t* mx, int splits, void* workspace, size_t workspace_bytes, void* stream);
 int dgq_gemm_mx_plan_splits(int M, int N, int Kp, size_t workspace_bytes);
 size_t dgq_gemm_mx_workspace_bytes(int M, int N, int Kp);
+
+/* ---- W8 weights under the real-time MX activation formats (W8A6 / W8A8; a mode of this library) ---------------------------------------
+ * For integer zero points d = q − z lies in [−255, 255]; with H = |d| >> 4 and L = |d| & 15, d = 32·(±H/2) + 2·(±L/2), and ±H/2, ±L/2 are
+ * E2M3 grid values: a W8 weight is two FP6 planes (the statement: dgq_amd/quant/quant_layer.py mxw8_split).
+ * dgq_pack_w_mx6x2: arguments and checks as dgq_pack_w_mx6 (codes [N][C·taps] in the reference order, zw [N] the integer zero points in
+ * the domain of `codes`; |q − z| <= 255 — the caller's check): packed [N][Kp/32][48 bytes] = per 32-block of the natural K order the H
+ * plane's 24 bytes, then the L plane's, each the 192-bit string of dgq_act_mx6_out_t; a zero magnitude is stored +0, the K padding 0.
+ * dgq_gemm_mxw8: the layer of dgq_gemm_mx6 (a_format 6: codes / scale = dgq_quant_act_mx6's, y = gamma + alpha·Σ 2^E·a·d) or of
+ * dgq_gemm_mxint8 (a_format 8: dgq_quant_act_mxint8's, y = gamma + alpha·Σ 2^(E−6)·s·d) against g->wpacked = that image (16-byte
+ * aligned).  Per 64-deep K step 2 (a_format 6) or 4 (a_format 8) block-scaled FP6 MFMAs into ONE fp32 accumulator over the whole K, in
+ * a fixed order, smallest scale first — weight-side scale bytes 128 (L), 132 (H); 123 (lo·L), 127 (hi·L), 127 (lo·H), 131 (hi·H).  Every
+ * product is exact; only the fp32 accumulation rounds.  Everything else — the fields of `g` that are read, rows, chunks, taps, ups, the
+ * Linear case, the epilogue forms — as for dgq_gemm_mx6.  dgq_gemm_mxw8_splitk: its K split, as dgq_gemm_mx6_splitk (same partial
+ * layout, combine kernel and plan: dgq_gemm_mx_plan_splits / dgq_gemm_mx_workspace_bytes). */
+int dgq_pack_w_mx6x2(const uint8_t* codes, const float* zw, int N, int C, int taps, int Kp, uint8_t* packed, void* stream);
+typedef struct dgq_gemm_mxw8 {
+    const uint8_t* scale; int lds;    /* the quantiser's scale / lds */
+    int B, H, W, C, kh, kw, stride, pad, ups;
+    int a_format;                     /* 6: MXFP6 codes (24 bytes per block); 8: MXINT8 codes (48 bytes per block) */
+} dgq_gemm_mxw8_t;
+int dgq_gemm_mxw8(const dgq_gemm_args_t* g, const dgq_gemm_mxw8_t* mx, void* stream);
+int dgq_gemm_mxw8_splitk(const dgq_gemm_args_t* g, const dgq_gemm_mxw8_t* mx, int splits, void* workspace, size_t workspace_bytes, void* stream);
 /* Small tile grids are split along K (deterministic: fp32 partial slabs [S][M][N] in the caller's `workspace`,
  * summed in a fixed order by a second kernel). dgq_gemm_workspace_bytes returns what the preferred split of a
  * shape needs; with workspace == NULL (or too small) fewer / no splits are used — results do not depend on it

@@ -25,6 +25,11 @@ each mode against the same model with un-quantised activations.
 --mxint8 measures the real-time MXINT8 mode (real_time_format="mxint8": dgq_quant_act_mxint8 + dgq_gemm_mxint8, W4A8) the same way, against
 the int8 block and row modes — profiles/r22_realtime_mxint8.txt:
     python tools/profile_realtime_act.py --mxint8 --out profiles/r22_realtime_mxint8.txt
+
+--mx-w8 measures W8 layers under both MX formats (real_time_mx_w8=True: dgq_gemm_mxw8 on the two-plane weight image, W8A6 / W8A8) against
+the route they take with the flag off (dgq_gemm_blockq at W8), which is captured twice: its own spread is the yardstick of "level" —
+profiles/r24_realtime_mx_w8.txt:
+    python tools/profile_realtime_act.py --mx-w8 --out profiles/r24_realtime_mx_w8.txt
 """
 import argparse
 import gc
@@ -231,22 +236,58 @@ def mx_ksplit_table(torch, ops, dev, lines, fmt, sweep=(2, 4, 8, 16)):
     lines.append("largest plan workspace over these shapes: %.1f MB of ops.WORKSPACE_BYTES = %d MB" % (worst_ws / 2 ** 20, ops.WORKSPACE_BYTES >> 20))
 
 
-def build_rt_model(torch, arch, fmt, abits, steps_cfg, batch, res, dev, use_aq=True):
-    """a real-time model of ``arch`` from a weight-only checkpoint at W4 / ``abits``: fmt "row", "block" or "mxfp6"; use_aq False: the
-    weight-only state (un-quantised activations)"""
+def mxw8_kernel_table(torch, ops, dev, lines, fmt):
+    """dgq_gemm_mxw8 under ``fmt`` activations, by the plan's K split as the layers run it, against dgq_gemm_blockq at W8 and the same bit
+    width (captured twice), with both quantisers, per SD layer shape of mx_kernel_table"""
+    from dgq_amd import synth
+    ab = 8 if fmt == "mxint8" else 6
+    quant_mx = ops.quant_act_mxint8 if fmt == "mxint8" else ops.quant_act_mx6
+    lines += ["", "layer shapes of an SD1.4 step (fp32, W8A%d, %s activations; 20 calls per hipGraph replay, median of 7 ALTERNATING rounds); on = dgq_gemm_mxw8"
+              % (ab, fmt.upper()), "(the plan's K split), off = dgq_gemm_blockq twice (off, off'); level: on within [min, max] of the two off medians",
+              "%-34s %8s %8s %8s %8s %8s %8s %8s  %s" % ("layer", "on q us", "on g us", "off q us", "off g us", "off' g us", "g on/off", "pair", "GEMM")]
+    g = torch.Generator().manual_seed(0)
+    verdicts = {}
+    for name, geom, N, _ups in KSPLIT_SHAPES[:13]:
+        B, H, W, C, kh, kw, stride, pad = geom
+        taps = kh * kw
+        w = torch.randn(N, C * taps, generator=g) * (C * taps) ** -0.5
+        wd, wz = synth.channel_minmax(w, 8)
+        pw = ops.PackedWeight(w.to(dev), wd.to(dev), wz.to(dev), None, torch.zeros(N).to(dev), 8, C, taps)
+        mxb, blk = ops.MxActBinding(pw, fmt, w_bits=8), ops.BlockActBinding(pw, ab)
+        x = (torch.randn(B, H, W, C, generator=g) * 1.3 + 0.2).to(dev)
+        pad_k = blk.Kp // 32 if taps == 1 else C // 32
+        qm, qb = quant_mx(x, geom, lds=pad_k), ops.quant_act_block(x, geom, ab, ldt=pad_k)
+        off = lambda: captured(torch, lambda: ops.gemm_blockq(qb, geom, blk, torch.float32))
+        graphs = dict(mq=captured(torch, lambda: quant_mx(x, geom, lds=pad_k)), mg=captured(torch, lambda: ops._block_gemm(mxb, qm, geom, torch.float32)),
+                      bq=captured(torch, lambda: ops.quant_act_block(x, geom, ab, ldt=pad_k)), bg=off(), bg2=off())
+        us = alternating_us(torch, graphs)
+        lo, hi = sorted((us["bg"], us["bg2"]))
+        verdict = "faster" if us["mg"] < lo else "level" if us["mg"] <= hi else "SLOWER"
+        verdicts.setdefault(verdict, []).append(name)
+        lines.append("%-34s %8.2f %8.2f %8.2f %8.2f %8.2f %8.2f %8.2f  %s" % (name, us["mq"], us["mg"], us["bq"], us["bg"], us["bg2"], us["mg"] / ((lo + hi) / 2),
+                                                                         (us["mq"] + us["mg"]) / (us["bq"] + (lo + hi) / 2), verdict))
+        del graphs
+    lines.append("; ".join("%s: %s" % (k, ", ".join(v)) for k, v in verdicts.items()))
+
+
+def build_rt_model(torch, arch, fmt, abits, steps_cfg, batch, res, dev, use_aq=True, wbits=4, mx_w8=False):
+    """a real-time model of ``arch`` from a weight-only checkpoint at W``wbits`` / ``abits``: fmt "row", "block", "mxfp6" or "mxint8"
+    (mx_w8: with real_time_mx_w8=True); use_aq False: the weight-only state (un-quantised activations)"""
     import bench
     from dgq_amd import synth
     from dgq_amd.diffusers_rewrite import UNet2DConditionModel
     from dgq_amd.quant import get_qmodel, Scaler
     from dgq_amd.runtime import quant_params
     cfg = dict(bench.CONFIGS["c2"]["cfg"])
-    path = "/tmp/dgq_synth_%s_w4a%d_weight_only.pth" % (arch, abits)
+    path = "/tmp/dgq_synth_%s_w%da%d_weight_only.pth" % (arch, wbits, abits)
     if not os.path.exists(path):
-        synth.write_cali_ckpt(path, arch, 4, abits, 1, num_slots=1, seed=0, batch=batch, res=res, with_act=False)
+        synth.write_cali_ckpt(path, arch, wbits, abits, 1, num_slots=1, seed=0, batch=batch, res=res, with_act=False)
     unet = UNet2DConditionModel(arch)
     unet.load_state_dict(synth.state_dict_from_ckpt(path))
-    wq, aq, sm = quant_params(Scaler, 4, abits, True, cfg["log"], cfg["rt"], cfg["sp"])
+    wq, aq, sm = quant_params(Scaler, wbits, abits, True, cfg["log"], cfg["rt"], cfg["sp"])
     aq["real_time"] = True
+    if mx_w8:
+        aq["real_time_mx_w8"] = True
     if fmt != "row":
         aq["real_time_block"] = 32
     if fmt in ("mxfp6", "mxint8"):
@@ -263,8 +304,9 @@ MX_MODES = (("row", "real-time rows, A6"), ("block", "real-time blocks of 32, A6
 MXINT8_MODES = (("row", "real-time rows, A8"), ("block", "real-time blocks of 32, A8 (int)"), ("mxint8", "real-time MXINT8 blocks, A8"))
 
 
-def mx_step_table(torch, ops, args, dev, lines, modes=MX_MODES, ab=6):
-    """the SD step in the three real-time modes at W4A6 (MXINT8_MODES: W4A8), alternating rounds of one process"""
+def mx_step_table(torch, ops, args, dev, lines, modes=MX_MODES, ab=6, build=None, wbits=4):
+    """the SD step in the three real-time modes at W4A6 (MXINT8_MODES: W4A8), alternating rounds of one process.  build(mode) -> model
+    replaces the W4 models; a mode "<m>#2" is the model and graphs of mode "<m>" timed in a second slot of every round"""
     from dgq_amd import synth
     from dgq_amd.runtime import DDIMScheduler
     sched = DDIMScheduler(50).timesteps
@@ -275,8 +317,11 @@ def mx_step_table(torch, ops, args, dev, lines, modes=MX_MODES, ab=6):
     ctx = synth.named_randn("ctx", (2, 77, 768), 100).to(dev)
     models, info = {}, {}
     for mode, _label in modes:
+        if mode.endswith("#2"):
+            models[mode], info[mode] = models[mode[:-2]], info[mode[:-2]][:2] + ([],)
+            continue
         ops.MX_KSPLIT = 1 if mode.endswith("@1") else None     # "<fmt>@1": the MX mode captured with its K split off (the plan is read at capture)
-        qnn = build_rt_model(torch, "sd", mode.split("@")[0], ab, 50, 2, 64, dev)
+        qnn = build(mode) if build else build_rt_model(torch, "sd", mode.split("@")[0], ab, 50, 2, 64, dev)
 
         def one_step(x, t, qnn=qnn):
             eps = qnn(torch.cat([x, x], dim=0), t, ctx)[0]
@@ -310,8 +355,9 @@ def mx_step_table(torch, ops, args, dev, lines, modes=MX_MODES, ab=6):
                 torch.cuda.synchronize()
                 info[mode][2].append((time.perf_counter() - t0) / args.steps * 1e3)
                 assert torch.isfinite(x).all()
-    lines += ["", "SD1.4-size synthetic model, 512^2 (64x64 latents), CFG pair, fp32, W4A%d, weight-only checkpoint; hipGraph replay, %d timed steps behind"
-              % (ab, args.steps), "%d warm-up steps per window, %d ALTERNATING rounds (rows, blocks, MX blocks, rows, ...) in one process on one box" % (args.warmup, args.windows),
+    lines += ["", "SD1.4-size synthetic model, 512^2 (64x64 latents), CFG pair, fp32, W%dA%d, weight-only checkpoint; hipGraph replay, %d timed steps behind"
+              % (wbits, ab, args.steps), "%d warm-up steps per window, %d ALTERNATING rounds (%s, %s, ...) in one process on one box"
+              % (args.warmup, args.windows, ", ".join(m for m, _ in modes) if build else "rows, blocks, MX blocks", modes[0][0] if build else "rows"),
               "%-44s %10s %10s %10s %12s" % ("mode", "median ms", "min ms", "max ms", "entry calls")]
     args.rounds_log = [info[mode][2] for mode, _ in modes]     # per mode, the rounds in order
     for mode, label in modes:
@@ -485,6 +531,7 @@ def main(argv=None):
     ap.add_argument("--mx", action="store_true", help="measure the real-time MXFP6 mode (see the head of this file)")
     ap.add_argument("--mxint8", action="store_true", help="measure the real-time MXINT8 mode (see the head of this file)")
     ap.add_argument("--mx-ksplit", action="store_true", help="measure the K split of the two MX GEMMs: per shape, and (without --kernels-only) per step")
+    ap.add_argument("--mx-w8", action="store_true", help="measure W8 layers under both MX formats, flag on against flag off (see the head of this file)")
     ap.add_argument("--append", default=None, help="--mx / --mxint8: a text file whose lines are appended to the report (the tests' measured constants)")
     args = ap.parse_args(argv)
     import torch
@@ -493,6 +540,26 @@ def main(argv=None):
     _lib.require_gpu()
     torch.set_num_threads(min(torch.get_num_threads(), 16))
     dev = torch.device("cuda", 0)
+    if args.mx_w8:
+        lines = ["W8 layers under the real-time MX formats (real_time_mx_w8=True: dgq_gemm_mxw8, W8A6 / W8A8) — tools/profile_realtime_act.py --mx-w8",
+                 "commit %s; %s; torch %s; ABI %d" % (args.stamp or stamp_default(), torch.cuda.get_device_name(0), torch.__version__, _lib.ABI_VERSION)]
+        for fmt, ab in (("mxfp6", 6), ("mxint8", 8)):
+            mxw8_kernel_table(torch, ops, dev, lines, fmt)
+        for fmt, ab in (() if args.kernels_only else (("mxfp6", 6), ("mxint8", 8))):
+            modes = (("off", "%s asked, flag off (int blocks, A%d)" % (fmt.upper(), ab)), ("on", "%s, real_time_mx_w8=True" % fmt.upper()), ("off#2", "flag off, second slot"))
+            mx_step_table(torch, ops, args, dev, lines, modes, ab, build=lambda m: build_rt_model(torch, "sd", fmt, ab, 50, 2, 64, dev, wbits=8, mx_w8=m == "on"), wbits=8)
+            lines.append("per round (ms), off | on | off#2: " + "; ".join("%.3f | %.3f | %.3f" % p for p in zip(*args.rounds_log)))
+            ops._WORKSPACE.clear()
+            gc.collect()
+            torch.cuda.empty_cache()
+        if args.append:
+            lines += [""] + open(args.append).read().splitlines()
+        text = "\n".join(lines) + "\n"
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text)
+        print(text)
+        return 0
     if args.mx_ksplit:
         lines = ["K split of the block-scaled MX GEMMs (dgq_gemm_mx6_splitk / dgq_gemm_mxint8_splitk) — tools/profile_realtime_act.py --mx-ksplit",
                  "commit %s; %s; torch %s; ABI %d" % (args.stamp or stamp_default(), torch.cuda.get_device_name(0), torch.__version__, _lib.ABI_VERSION)]
