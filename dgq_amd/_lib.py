@@ -38,6 +38,10 @@ SIGNATURES = {
     "dgq_conv2d_wq": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp],
     "dgq_conv2d_wq_mfma16": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp],
     "dgq_conv2d_wq_mfma16_fused": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp],
+    "dgq_conv2d_wq_mfma16_splitk": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i,
+                                    _i, _vp, ctypes.c_size_t, _vp],
+    "dgq_conv2d_wq_mfma16_plan_splits": [_i, _i, _i, _i, ctypes.c_size_t],
+    "dgq_conv2d_wq_mfma16_workspace_bytes": [_i, _i, _i, _i],
     "dgq_layernorm_row_stats": [_vp, _i, _i, _i, _f, _vp, _vp],
     "dgq_attention_mfma16": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
     "dgq_attention_mfma16_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],

@@ -8,7 +8,16 @@
 //   bf16 x: V_MFMA_F32_32X32X16_BF16 / 16X16X32_BF16, x̃ = x;      f16 x: the _F16 forms, x̃ = x;
 //   fp32 x: two bf16 terms, hi = bf16_rn(x), lo = bf16_rn(x − hi): two MFMAs per K step into the same accumulator, first lo, then hi;
 //           x̃ = hi + lo, |x − x̃| <= 2^-16·|x| (the attention kernels' split, attn_bf16x3_dev.h, with two terms).
-// One K loop per workgroup: no K split, no atomics, nothing exchanged between workgroups; the order is fixed by the shape.
+// One K loop per workgroup, nothing exchanged between workgroups; the order of summation is fixed by the shape.
+//
+// The K split (dgq_conv2d_wq_mfma16_splitk): the long-K convolutions of the 8x8 / 16x16 UNet levels (M = 128 .. 512, K = 11 520 ..
+// 23 040) are 160 .. 640 workgroups that each walk 90 .. 180 K tiles strictly in series — a latency chain, not bandwidth.  Split S ways
+// the grid is (row tiles, column tiles, S): workgroup z walks K tiles [z·tps, min(T, (z + 1)·tps)) with the same staging, double
+// buffering and MFMAs (KS = true of the one body below; its running tap state starts at the split's first tile) and leaves, instead of
+// the epilogue, its raw fp32 accumulator in the caller's workspace, [split][tile][wave][quad][lane] as float4: 1 KiB per wave and quad
+// in a row.  wq16_combine_kernel, a second launch on the tile grid in the same wave and lane roles, adds each wave's S partials in
+// ascending split order and runs the un-split epilogue on the sum.  The kernel boundary is the only exchange: no atomics, no counters,
+// no spinning; one fixed order, equal to the un-split result bit for bit wherever fp32 addition is exact.
 //
 // 256 threads (2 x 2 waves, one MFMA tile each); K tiles of BK through a double-buffered LDS held in the operand type (rows of
 // BK + 8 elements: the 16-byte fragment reads of 16 consecutive rows fall on distinct banks), global loads of tile t+2 in flight
@@ -99,8 +108,18 @@ struct Wq16ProRegs : Wq16Regs<U, NA> {
     uint32_t ok[U];
 };
 
-template <int MF, int BK, bool F16, bool SPLIT, int FUSE>
-__device__ __forceinline__ void wq16_gemm_body(const std::conditional_t<FUSE != 0, Wq16FusedParams, Wq16Params>& p) {
+// first float4 of wave `wid`, lane `lane` in the partial of this workgroup's tile under split s (NQ register quads per lane: quad j at + 64·j)
+template <int NQ>
+__device__ __forceinline__ int64_t wq16_partial_at(int s, int wid, int lane) {
+    const int64_t tile = (int64_t)blockIdx.y * gridDim.x + blockIdx.x, tiles = (int64_t)gridDim.x * gridDim.y;
+    return (((int64_t)s * tiles + tile) * 4 + wid) * (NQ * 64) + lane;
+}
+
+// KS: the split form — K tiles [blockIdx.z·tps, min(T, (blockIdx.z + 1)·tps)), the accumulator to `part` instead of the epilogue
+template <int MF, int BK, bool F16, bool SPLIT, int FUSE, bool KS = false>
+__device__ __forceinline__ void wq16_gemm_body(const std::conditional_t<FUSE != 0, Wq16FusedParams, Wq16Params>& p, float4* part = nullptr,
+                                               int tps = 0) {
+    static_assert(!KS || FUSE == 0, "the fused entry is not split");
     using Cfg = Wq16Cfg<MF, BK, F16, SPLIT>;
     constexpr int BM = Cfg::BM, U = Cfg::U, NA = Cfg::NA, CPR = Cfg::CPR, RPP = Cfg::RPP, PITCH = Cfg::PITCH, NACC = Cfg::NACC;
     constexpr bool PRO = FUSE == 2;
@@ -149,10 +168,19 @@ __device__ __forceinline__ void wq16_gemm_body(const std::conditional_t<FUSE != 
     constexpr int XSZ = SPLIT ? 4 : 2;
     const bool avec = (p.C & 7) == 0 && (reinterpret_cast<uintptr_t>(p.x) & 15) == 0;
     // (tap, c) of this thread's first k in the next tile to load, advanced by BK per tile (no division per element)
+    const int T = (p.K + BK - 1) / BK;
+    const int t0 = KS ? blockIdx.z * tps : 0, t1 = KS ? min(T, t0 + tps) : T;     // this workgroup's K tiles
     int tc = 8 * ju, tdh = 0, tdw = 0;
-    while (tc >= p.C) {
-        tc -= p.C;
-        if (++tdw == p.kw) { tdw = 0; ++tdh; }
+    if constexpr (KS) {                                   // a split may begin anywhere in a tap: one division per thread
+        const int k0 = t0 * BK + 8 * ju, tap = k0 / p.C;
+        tc = k0 - tap * p.C;
+        tdh = tap / p.kw;
+        tdw = tap - tdh * p.kw;
+    } else {
+        while (tc >= p.C) {
+            tc -= p.C;
+            if (++tdw == p.kw) { tdw = 0; ++tdh; }
+        }
     }
 
     bool bn_ok[U];
@@ -168,7 +196,6 @@ __device__ __forceinline__ void wq16_gemm_body(const std::conditional_t<FUSE != 
         bswap[i] = (p.w_bits == 4 && (n & 16)) ? 2 : 0;              // layout 1: rows with n & 16 keep word w at w ^ 2
     }
 
-    const int T = (p.K + BK - 1) / BK;
     const uint8_t* xb = reinterpret_cast<const uint8_t*>(p.x);
 
     auto pixel = [&](int i, int hi, int wi) -> int64_t {
@@ -351,20 +378,29 @@ __device__ __forceinline__ void wq16_gemm_body(const std::conditional_t<FUSE != 
 
     // ---- main loop: two register sets, loads of tile t+2 issued before tile t is multiplied
     Regs r0, r1;
-    load_tile(0, r0);
-    if (T > 1) load_tile(1, r1);
-    store_tile(0, 0, r0);
+    load_tile(t0, r0);
+    if (t0 + 1 < t1) load_tile(t0 + 1, r1);
+    store_tile(t0, 0, r0);
     __syncthreads();
-    for (int t = 0; t < T; t += 2) {
-        if (t + 2 < T) load_tile(t + 2, r0);
+    for (int t = t0; t < t1; t += 2) {
+        if (t + 2 < t1) load_tile(t + 2, r0);
         compute(0);
-        if (t + 1 < T) store_tile(t + 1, 1, r1);
+        if (t + 1 < t1) store_tile(t + 1, 1, r1);
         __syncthreads();
-        if (t + 1 >= T) break;
-        if (t + 3 < T) load_tile(t + 3, r1);
+        if (t + 1 >= t1) break;
+        if (t + 3 < t1) load_tile(t + 3, r1);
         compute(1);
-        if (t + 2 < T) store_tile(t + 2, 0, r0);
+        if (t + 2 < t1) store_tile(t + 2, 0, r0);
         __syncthreads();
+    }
+
+    if constexpr (KS) {
+        // ---- the split's partial: the raw accumulator in its own order, 16-byte stores, a wave's 64 lanes on 1 KiB in a row; ragged
+        // tiles whole (rows m >= M and columns n >= N accumulated zeros: the combine masks them as the un-split epilogue does)
+        float4* dst = part + wq16_partial_at<NACC / 4>(blockIdx.z, wid, lane);
+#pragma unroll
+        for (int j = 0; j < NACC / 4; ++j) dst[64 * j] = make_float4(acc[4 * j], acc[4 * j + 1], acc[4 * j + 2], acc[4 * j + 3]);
+        return;
     }
 
     if constexpr (FUSE != 0) {
@@ -411,6 +447,57 @@ template <int MF, int BK, bool F16, bool SPLIT>
 __global__ __launch_bounds__(256) void wq16_gemm_kernel(Wq16Params p) { wq16_gemm_body<MF, BK, F16, SPLIT, 0>(p); }
 template <int MF, int BK, bool F16, bool SPLIT, int FUSE>
 __global__ __launch_bounds__(256) void wq16_gemm_fused_kernel(Wq16FusedParams p) { wq16_gemm_body<MF, BK, F16, SPLIT, FUSE>(p); }
+template <int MF, int BK, bool F16, bool SPLIT>
+__global__ __launch_bounds__(256) void wq16_gemm_split_kernel(Wq16Params p, float4* part, int tps) {
+    wq16_gemm_body<MF, BK, F16, SPLIT, 0, true>(p, part, tps);
+}
+
+// Sum of the S partials of one register quad in ascending split order, R loads in flight per round (splitk_sum of gemm_tile.h, whose
+// BK collides with this file's template parameter: a load per iteration of a runtime-bounded loop would be S dependent round trips)
+template <int R>
+__device__ __forceinline__ void wq16_sum_partials(const float4* base, int64_t stride, int splits, float (&a)[4]) {
+    for (int s0 = 0; s0 < splits; s0 += R) {
+        float4 v[R];
+#pragma unroll
+        for (int j = 0; j < R; ++j) v[j] = base[(int64_t)min(s0 + j, splits - 1) * stride];
+#pragma unroll
+        for (int j = 0; j < R; ++j)
+            if (s0 + j < splits) { a[0] += v[j].x; a[1] += v[j].y; a[2] += v[j].z; a[3] += v[j].w; }
+    }
+}
+
+// The second launch of a split layer. Grid = the tile grid, 256 threads in the GEMM's roles: wave w reads ITS OWN S partials — per
+// register quad one coalesced 1 KiB row per split, the S loads of a quad in flight together (splitk_sum) — adds them in ascending split
+// order into the registers the un-split kernel holds behind its K loop, and runs that kernel's epilogue, expression for expression.
+template <int MF>
+__global__ __launch_bounds__(256) void wq16_combine_kernel(Wq16Params p, const float4* part, int splits) {
+    constexpr int BM = 2 * MF, NACC = MF == 32 ? 16 : 4;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BM;
+    const int wm = (wid >> 1) * MF, wn = (wid & 1) * MF;
+    const int lr = lane % MF, lk = lane / MF;
+    const int n = n0 + wn + lr;
+    if (n >= p.N) return;
+    const float4* src = part + wq16_partial_at<NACC / 4>(0, wid, lane);
+    const int64_t stride = (int64_t)gridDim.x * gridDim.y * (NACC * 64);         // float4 between the splits of one tile
+    float acc[NACC];
+#pragma unroll
+    for (int j = 0; j < NACC / 4; ++j) {
+        float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (splits <= 4) wq16_sum_partials<4>(src + 64 * j, stride, splits, a);  // (uniform branches: splits is a kernel argument)
+        else if (splits <= 8) wq16_sum_partials<8>(src + 64 * j, stride, splits, a);
+        else wq16_sum_partials<16>(src + 64 * j, stride, splits, a);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[4 * j + k] = a[k];
+    }
+    const float dn = p.delta[n], bias = p.bias ? p.bias[n] : 0.0f;
+    const int col = p.geglu ? ((n >> 1) + (n & 1) * (p.N >> 1)) : n;
+#pragma unroll
+    for (int e = 0; e < NACC; ++e) {
+        const int m = m0 + wm + (MF == 32 ? (e & 3) + 8 * (e >> 2) + 4 * lk : 4 * lk + e);
+        if (m < p.M) wq16_store(p.y, p.y_dtype, (int64_t)m * p.ldy + col, dn * acc[e] + bias);
+    }
+}
 
 // Tile choice (MI355X: 256 CUs), measured with each form forced on the 49 layer shapes of the SD UNet: the 64 x 64 form is the faster
 // one where it launches at least one workgroup per CU (it stages half the bytes per output element), the 32 x 32 form everywhere
@@ -481,6 +568,114 @@ extern "C" int dgq_conv2d_wq_mfma16(const void* x, int x_dtype, int B, int H, in
     if (tile == 64) wq16_launch<32, 64>(p, x_dtype, (hipStream_t)stream);
     else wq16_launch<16, 128>(p, x_dtype, (hipStream_t)stream);
     return dgq_launch_status("dgq_conv2d_wq_mfma16");
+}
+
+// ---- the K split: geometry, plan and entry
+struct Wq16SplitGeom {
+    int tile, T;                  // the tile form of the shape (wq16_pick) and its K tiles
+    int64_t tiles;                // output tiles
+    size_t part_bytes;            // one partial: 4 waves x (1 or 4) quads x 64 lanes x 16 bytes
+};
+static Wq16SplitGeom wq16_split_geom(int M, int N, int K) {
+    Wq16SplitGeom g;
+    g.tile = wq16_pick(M, N);
+    const int bk = g.tile == 64 ? 64 : 128;
+    g.T = (K + bk - 1) / bk;
+    g.tiles = (int64_t)((M + g.tile - 1) / g.tile) * ((N + g.tile - 1) / g.tile);
+    g.part_bytes = g.tile == 64 ? 16384 : 4096;
+    return g;
+}
+// S requested -> S launched: at most one split per K tile, and no split empty (the formula of block_split_plan, gemm_mx_split.hip)
+static int wq16_split_clamp(int s, int T) {
+    if (s > T) s = T;
+    if (s <= 1) return 1;
+    const int tps = (T + s - 1) / s;
+    return (T + tps - 1) / tps;
+}
+
+// The plan, from the forced-S sweep of profiles/r25_weight_only_ksplit.txt (S in 1 2 3 4 6 8 12 16 on the 49 layer shapes of the SD
+// UNet, bf16 and fp32 states, W4; the pair of launches against the un-split launch in alternating graph replays).  T = K tiles.
+//  32 x 32 form (T of 128): S = min(2560 / tiles, T / 5, 16).  With fewer tiles than CUs (160: M = 128) every row from T = 20 up gained
+//    (43 -> 21 us at T = 20, 140 -> 46 at T = 90, 274 -> 77 at T = 180) and S = 4 .. 16 lay within a few us of one another; at 320 .. 640
+//    tiles (M = 512) S = 4 .. 8 took 10 % .. 40 % off every row from T = 40 up, while T <= 23 gained nothing beyond the spread in one
+//    state or the other.  Rows with T < 20 — the M = 2 time-embedding layers (14 -> 7 us) and the M = 154 k / v projections (11 -> 8) —
+//    gained too but stay one launch: nothing below T = 20 was measured on other tile counts.
+//  64 x 64 form (T of 64): S = 4 or nothing.  16-bit x: up to 320 tiles from T = 20 (56 -> 47 us at T = 20, 157 -> 95 at T = 90, 447 ->
+//    247 at T = 270), up to 640 tiles from T = 90 (277 -> 262, 320 -> 284); S = 2 lost at 640 tiles and the 1280-tile rows gained 5 % at
+//    best.  fp32 x (two MFMAs per step, half the workgroups per CU): up to 640 tiles from T = 20 (101 -> 76, 665 -> 447, 702 -> 476), and
+//    S = 2 up to 1280 tiles (568 -> 492, 141 -> 128).
+//  Everything else, K of one or two tiles included, stays one launch.  At most 2560 x 4 KiB / 1280 x 2 x 16 KiB = 40 MiB of partials.
+constexpr int WQS_MAX = 16;
+constexpr int WQS_TARGET32 = 2560, WQS_TPS32 = 5, WQS_MIN_T32_FEW = 20, WQS_MIN_T32 = 40, WQS_CUS = 256;
+constexpr int WQS_S64 = 4, WQS_MIN_T64 = 20, WQS_MIN_T64_WIDE16 = 90, WQS_TILES64 = 320;
+static int wq16_split_plan(int M, int N, int K, int x_dtype, size_t workspace_bytes) {
+    const Wq16SplitGeom g = wq16_split_geom(M, N, K);
+    const int64_t fit = (int64_t)(workspace_bytes / ((size_t)g.tiles * g.part_bytes));
+    int64_t s = 1;
+    if (g.tile == 32) {
+        if (g.T < (g.tiles < WQS_CUS ? WQS_MIN_T32_FEW : WQS_MIN_T32)) return 1;
+        s = WQS_TARGET32 / g.tiles;
+        if (s > g.T / WQS_TPS32) s = g.T / WQS_TPS32;
+        if (s > WQS_MAX) s = WQS_MAX;
+        if (s > fit) s = fit;
+    } else {
+        const bool f32 = x_dtype == DGQ_F32;
+        if (g.T < WQS_MIN_T64) return 1;
+        if (g.tiles <= WQS_TILES64) s = WQS_S64;
+        else if (g.tiles <= 2 * WQS_TILES64) s = (f32 || g.T >= WQS_MIN_T64_WIDE16) ? WQS_S64 : 1;
+        else if (g.tiles <= 4 * WQS_TILES64) s = f32 ? WQS_S64 / 2 : 1;
+        if (s > fit) return 1;                            // a narrower split than the measured one is not taken
+    }
+    return wq16_split_clamp((int)s, g.T);
+}
+
+extern "C" int dgq_conv2d_wq_mfma16_plan_splits(int M, int N, int K, int x_dtype, size_t workspace_bytes) {
+    if (M <= 0 || N <= 0 || K <= 0) return 1;
+    return wq16_split_plan(M, N, K, x_dtype, workspace_bytes);
+}
+
+extern "C" size_t dgq_conv2d_wq_mfma16_workspace_bytes(int M, int N, int K, int x_dtype) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    const int s = wq16_split_plan(M, N, K, x_dtype, (size_t)-1);
+    const Wq16SplitGeom g = wq16_split_geom(M, N, K);
+    return s > 1 ? (size_t)s * g.tiles * g.part_bytes : 0;
+}
+
+template <int MF, int BK>
+static void wq16_launch_split(const Wq16Params& p, int x_dtype, int s, int tps, float4* part, hipStream_t stream) {
+    constexpr int BM = 2 * MF;
+    const dim3 tiles((p.M + BM - 1) / BM, (p.N + BM - 1) / BM), grid(tiles.x, tiles.y, s);
+    if (x_dtype == DGQ_F32) hipLaunchKernelGGL((wq16_gemm_split_kernel<MF, BK, false, true>), grid, dim3(256), 0, stream, p, part, tps);
+    else if (x_dtype == DGQ_F16) hipLaunchKernelGGL((wq16_gemm_split_kernel<MF, BK, true, false>), grid, dim3(256), 0, stream, p, part, tps);
+    else hipLaunchKernelGGL((wq16_gemm_split_kernel<MF, BK, false, false>), grid, dim3(256), 0, stream, p, part, tps);
+    hipLaunchKernelGGL(wq16_combine_kernel<MF>, tiles, dim3(256), 0, stream, p, (const float4*)part, s);
+}
+
+extern "C" int dgq_conv2d_wq_mfma16_splitk(const void* x, int x_dtype, int B, int H, int W, int C, int kh, int kw, int stride, int pad, int upsample,
+                                           const uint8_t* w_packed, int w_bits, int Kp, const float* delta, const float* zp, const float* bias,
+                                           int N, int geglu_rows, void* y, int y_dtype, int ldy, int splits, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    static const char* who = "dgq_conv2d_wq_mfma16_splitk";
+    Wq16Params p;
+    int tile = 0;
+    if (int rc = wq16_setup(who, x, x_dtype, B, H, W, C, kh, kw, stride, pad, upsample, w_packed, w_bits, Kp, delta, zp, bias,
+                            N, geglu_rows, y, y_dtype, ldy, N, p, tile)) return rc;
+    const Wq16SplitGeom g = wq16_split_geom(p.M, N, p.K);
+    const int s = wq16_split_clamp(splits, g.T);
+    if (s <= 1) {                                         // the un-split launch itself; no workspace is looked at
+        if (tile == 64) wq16_launch<32, 64>(p, x_dtype, (hipStream_t)stream);
+        else wq16_launch<16, 128>(p, x_dtype, (hipStream_t)stream);
+        return dgq_launch_status(who);
+    }
+    DGQ_CHECK_ARG(s <= 65535, "%s: splits=%d", who, s);
+    const size_t need = (size_t)s * g.tiles * g.part_bytes;
+    DGQ_CHECK_ARG(workspace && workspace_bytes >= need, "%s: %d splits need a workspace of %zu bytes (got %zu%s)", who, s, need,
+                  workspace ? workspace_bytes : (size_t)0, workspace ? "" : ": null pointer");
+    DGQ_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+    const int tps = (g.T + s - 1) / s;
+    if (tile == 64) wq16_launch_split<32, 64>(p, x_dtype, s, tps, reinterpret_cast<float4*>(workspace), (hipStream_t)stream);
+    else wq16_launch_split<16, 128>(p, x_dtype, s, tps, reinterpret_cast<float4*>(workspace), (hipStream_t)stream);
+    return dgq_launch_status(who);
 }
 
 extern "C" int dgq_conv2d_wq_mfma16_fused(const void* x, int x_dtype, int B, int H, int W, int C, int kh, int kw, int stride, int pad, int upsample,

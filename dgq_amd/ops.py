@@ -1417,11 +1417,19 @@ def conv2d_wq(x: torch.Tensor, pw: PackedWeight, kh, kw, stride, pad, upsample=F
     return result(y)
 
 
-def conv2d_wq_mfma16(x: torch.Tensor, pw: PackedWeight, kh, kw, stride, pad, upsample=False, geglu_rows=False):
+#: the K split of the weight-only matrix-core layers (QuantLayer's route to conv2d_wq_mfma16): None = the library's plan per shape
+#: (dgq_conv2d_wq_mfma16_plan_splits), 1 = never, an int = forced — in the manner of MX_KSPLIT
+WQ16_KSPLIT = None
+
+
+def conv2d_wq_mfma16(x: torch.Tensor, pw: PackedWeight, kh, kw, stride, pad, upsample=False, geglu_rows=False, ksplit=None):
     """Weight-only state on the bf16 / f16 matrix cores (dgq_conv2d_wq_mfma16), beside conv2d_wq: the same operands, arguments and
     returned views, NOT the same bits — y = b + δ·Σ_k x̃·(q − z) with the integer q − z as the 16-bit operand, fp32 accumulation in
     the kernel's own order and δ in the epilogue.  bf16 / f16 x enter as they are; fp32 x as two bf16 terms (|x − x̃| <= 2^-16·|x|).
-    pw.mfma16_eligible() must hold (the caller's check: QuantLayer routes an ineligible weight to conv2d_wq)."""
+    pw.mfma16_eligible() must hold (the caller's check: QuantLayer routes an ineligible weight to conv2d_wq).
+    ksplit: None the plan's K split (dgq_conv2d_wq_mfma16_plan_splits within workspace(device)), 1 never, an int a forced one —
+    dgq_conv2d_wq_mfma16_splitk, the split launch and its combine over workspace(device); a split result differs from the un-split
+    one in the order of the fp32 summation only."""
     assert pw.mfma16_eligible(), "dgq conv2d_wq_mfma16: q − z is not an integer within the operand's exact range"
     w_img, Kp = pw.natural()
     N = pw.N
@@ -1429,9 +1437,16 @@ def conv2d_wq_mfma16(x: torch.Tensor, pw: PackedWeight, kh, kw, stride, pad, ups
     B, H, W = geom[:3]
     M = B * ((H + 2 * pad - kh) // stride + 1) * ((W + 2 * pad - kw) // stride + 1)
     y = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    _lib_call("dgq_conv2d_wq_mfma16", _lib.ptr(xs), _lib.DTYPE_CODE[x.dtype], *geom, int(upsample),
-              _lib.ptr(w_img), pw.bits, Kp, _lib.ptr(pw.alpha), _lib.ptr(pw.zp_true), _lib.ptr(pw.bias), N, int(geglu_rows),
-              _lib.ptr(y), _lib.DTYPE_CODE[y.dtype], N, _lib.stream())
+    args = (_lib.ptr(xs), _lib.DTYPE_CODE[x.dtype], *geom, int(upsample),
+            _lib.ptr(w_img), pw.bits, Kp, _lib.ptr(pw.alpha), _lib.ptr(pw.zp_true), _lib.ptr(pw.bias), N, int(geglu_rows),
+            _lib.ptr(y), _lib.DTYPE_CODE[y.dtype], N)
+    if ksplit is None:                                      # the plan says un-split: the un-split entry, and no workspace is asked for
+        ksplit = _lib.load().dgq_conv2d_wq_mfma16_plan_splits(M, N, kh * kw * geom[3], _lib.DTYPE_CODE[x.dtype], WORKSPACE_BYTES)
+    if ksplit <= 1:
+        _lib_call("dgq_conv2d_wq_mfma16", *args, _lib.stream())
+    else:
+        ws = workspace(x.device)
+        _lib_call("dgq_conv2d_wq_mfma16_splitk", *args, int(ksplit), _lib.ptr(ws), ws.numel(), _lib.stream())
     return result(y)
 
 

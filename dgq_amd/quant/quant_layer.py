@@ -901,7 +901,9 @@ class QuantLayer(nn.Module):
         return self.weight_only_mfma16 and self.packed_weight().mfma16_eligible()
 
     def _weight_only_op(self):
-        return ops.conv2d_wq_mfma16 if self.takes_mfma16() else ops.conv2d_wq
+        if self.takes_mfma16():                             # with the K split ops.WQ16_KSPLIT asks for (None: the library's plan)
+            return lambda *a, **kw: ops.conv2d_wq_mfma16(*a, ksplit=ops.WQ16_KSPLIT, **kw)
+        return ops.conv2d_wq
 
     def takes_fused(self, x: torch.Tensor) -> bool:
         """True when the folding methods run dgq_conv2d_wq_mfma16_fused on x: the switch is set, the call is on the packed weight-only

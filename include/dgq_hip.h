@@ -53,7 +53,8 @@ extern "C" {
  *        matrix-core layer — and dgq_layernorm_row_stats; the real-time MXINT8 mode, dgq_quant_act_mxint8 / dgq_dequant_act_mxint8 /
  *        dgq_gemm_mxint8 with dgq_act_mxint8_out_t and dgq_gemm_mxint8_t; their K split (dgq_gemm_mx6_splitk, dgq_gemm_mxint8_splitk,
  *        dgq_gemm_mx_plan_splits, dgq_gemm_mx_workspace_bytes); W8 weights under both MX formats, dgq_pack_w_mx6x2 / dgq_gemm_mxw8 /
- *        dgq_gemm_mxw8_splitk with dgq_gemm_mxw8_t */
+ *        dgq_gemm_mxw8_splitk with dgq_gemm_mxw8_t; the K split of the weight-only matrix-core layer (dgq_conv2d_wq_mfma16_splitk,
+ *        dgq_conv2d_wq_mfma16_plan_splits, dgq_conv2d_wq_mfma16_workspace_bytes) — entries added only, the revision stays 123 */
 #define DGQ_ABI_VERSION 123
 int dgq_version(void);
 const char* dgq_last_error(void);
@@ -254,6 +255,23 @@ int dgq_conv2d_wq(const void* x, int x_dtype, int B, int H, int W, int C, int kh
 int dgq_conv2d_wq_mfma16(const void* x, int x_dtype, int B, int H, int W, int C, int kh, int kw, int stride, int pad, int upsample,
                          const uint8_t* w_packed, int w_bits, int Kp, const float* delta, const float* zp, const float* bias, int N,
                          int geglu_rows, void* y, int y_dtype, int ldy, void* stream);
+
+/* dgq_conv2d_wq_mfma16_splitk: dgq_conv2d_wq_mfma16 (the same arguments, check and statement) as a K split, for the long-K, low-M
+ * layers whose few workgroups would walk their K tiles in series.  Two launches: `splits` workgroups per output tile each walk
+ * ceil(T / splits) of the T K tiles (128 wide in the 32 x 32 form, 64 in the 64 x 64 form) and leave their raw fp32 accumulators in
+ * `workspace`; a combine on the tile grid adds the partials of a tile in ascending split order and runs the un-split epilogue.  No
+ * atomics: the order is fixed by (shape, splits), and the result equals the un-split one bit for bit wherever fp32 addition is exact.
+ * splits is clamped to T and so that no split is empty; splits <= 1 (after the clamp too) IS the un-split launch and looks at no
+ * workspace.  Otherwise the workspace must hold splits · tiles · (4 KiB | 16 KiB by tile form) bytes, 16-byte aligned: a NULL or
+ * smaller one is refused, the message names the bytes needed.  The caller owns it; launches that share it must be stream-ordered.
+ * dgq_conv2d_wq_mfma16_plan_splits: the measured choice for a shape (M = B·Ho·Wo, K = kh·kw·C) within workspace_bytes — 1 = stay
+ * un-split.  dgq_conv2d_wq_mfma16_workspace_bytes: what that choice needs with no limit (0 where it is 1). */
+int dgq_conv2d_wq_mfma16_splitk(const void* x, int x_dtype, int B, int H, int W, int C, int kh, int kw, int stride, int pad, int upsample,
+                                const uint8_t* w_packed, int w_bits, int Kp, const float* delta, const float* zp, const float* bias, int N,
+                                int geglu_rows, void* y, int y_dtype, int ldy, int splits, void* workspace, size_t workspace_bytes,
+                                void* stream);
+int dgq_conv2d_wq_mfma16_plan_splits(int M, int N, int K, int x_dtype, size_t workspace_bytes);
+size_t dgq_conv2d_wq_mfma16_workspace_bytes(int M, int N, int K, int x_dtype);
 
 /* dgq_conv2d_wq_mfma16_fused: dgq_conv2d_wq_mfma16 with the layer's element-wise neighbours folded into its load and its epilogue
  * (csrc/gemm_wonly16.hip).  Every pointer of `f` may be NULL; with f NULL or every field empty the call IS dgq_conv2d_wq_mfma16 (the

@@ -9,7 +9,8 @@ GPU box only:  python tools/bench_weight_only_mfma16.py [--bits 4 8] [--dtypes f
                                                          [--out FILE]      (e.g. profiles/r13_weight_only_mfma16.txt)
 DGQ_WQ16_TILE=32|64|128 in the environment forces one tile form of the new kernel for every shape (how wq16_pick was chosen).
 --fused measures QuantModel.set_weight_only_fused instead (run_fused below): python tools/bench_weight_only_mfma16.py --fused --bits 4
---dtypes bfloat16 float32 --out FILE      (profiles/r20_weight_only_fused.txt)"""
+--dtypes bfloat16 float32 --out FILE      (profiles/r20_weight_only_fused.txt)
+--ksplit measures the K split of the new kernel (run_ksplit below): the same arguments      (profiles/r25_weight_only_ksplit.txt)"""
 import argparse
 import collections
 import gc
@@ -283,6 +284,120 @@ def run_fused(arch, bits, res, batch, dtypes, whole, out):
     torch.cuda.empty_cache()
 
 
+KSPLITS = (1, 2, 3, 4, 6, 8, 12, 16)
+
+
+def run_ksplit(arch, bits, res, batch, dtypes, whole, out):
+    """The K split of dgq_conv2d_wq_mfma16 (dgq_conv2d_wq_mfma16_splitk).  Per distinct layer shape of one UNet call and per state: the
+    un-split launch against the pair of launches at every forced S of KSPLITS and at the plan's S, every graph replayed in turn in each
+    of ROUNDS rounds (median, and the spread min .. max of the un-split and of the planned one).  Then the whole call with
+    set_weight_only_mfma16 and the state's attention switch on: ops.WQ16_KSPLIT = 1 against the plan in alternating rounds."""
+    import statistics
+    p = lambda *a: (print(*a, flush=True), out.write(" ".join(str(s) for s in a) + "\n"))
+    lib = ops._lib.load()
+    qnn = build(arch, bits)
+    a = synth.ARCH[arch]
+    x = synth.named_randn("latent", (batch, 4, res, res), 1).cuda()
+    ctx = synth.named_randn("ctx", (batch, 77, a["ctx_dim"]), 100).cuda()
+    t = torch.full((1,), 999, dtype=torch.int64, device="cuda")
+    calls = collections.OrderedDict()
+    orig = ops.conv2d_wq
+
+    def rec(xx, pw, kh, kw, stride, pad, upsample=False, geglu_rows=False):
+        y = orig(xx, pw, kh, kw, stride, pad, upsample=upsample, geglu_rows=geglu_rows)
+        key = (y.numel() // pw.N, pw.N, pw.K, kh * kw, stride, bool(upsample))
+        if key not in calls:
+            calls[key] = dict(n=0, shape=tuple(xx.shape), pw=pw, g=(kh, kw, stride, pad, upsample))
+        calls[key]["n"] += 1
+        return y
+    ops.conv2d_wq = rec
+    try:
+        with torch.no_grad():
+            qnn(x, t, ctx)
+            torch.cuda.synchronize()
+    finally:
+        ops.conv2d_wq = orig
+    p("%s W%d, %dx%d latents, batch %d (CFG pair): %d weight-only layer calls, %d distinct shapes; tile forced: %s"
+      % (arch, bits, res, res, batch, sum(c["n"] for c in calls.values()), len(calls), os.environ.get("DGQ_WQ16_TILE", "no")))
+    for dt in dtypes:
+        name = str(dt).replace("torch.", "")
+        code = ops._lib.DTYPE_CODE[dt]
+        p("%s state: us per launch (S = 1) or per pair of launches, median of %d rounds; [min .. max] = the spread over the rounds" % (name, ROUNDS))
+        p("%7s %5s %6s %4s %3s %3s %5s %4s %4s |" % ("M", "N", "K", "taps", "st", "up", "calls", "tile", "T")
+          + "".join(" %7s" % ("S=%d" % s) for s in KSPLITS) + " | %19s | %4s %7s %19s %s" % ("S=1 spread", "plan", "us", "spread", "verdict"))
+        tot = [0.0, 0.0]
+        misses = []
+        for key, c in calls.items():
+            M, N, K, taps, stride, ups = key
+            kh, kw, st, pd, up = c["g"]
+            pw = c["pw"]
+            tile = int(os.environ.get("DGQ_WQ16_TILE", 0)) or (64 if ((M + 63) // 64) * ((N + 63) // 64) >= 256 else 32)     # wq16_pick
+            T = -(-K // (64 if tile == 64 else 128))
+            part = -(-M // tile) * -(-N // tile) * (16384 if tile == 64 else 4096)          # bytes of the partials of one split
+            plan = lib.dgq_conv2d_wq_mfma16_plan_splits(M, N, K, code, ops.WORKSPACE_BYTES)
+            xx = torch.randn(c["shape"], device="cuda").to(dt)
+            todo = [s for s in KSPLITS if s == 1 or (s <= T and s * part <= ops.WORKSPACE_BYTES)] + ([plan] if plan not in KSPLITS else [])
+            with torch.no_grad():
+                graphs = [graph_of(lambda s=s: ops.conv2d_wq_mfma16(xx, pw, kh, kw, st, pd, upsample=up, ksplit=s)) for s in todo]
+            ts = {s: [v * 1e3 for v in r] for s, r in zip(todo, _rounds_ms(graphs, ITERS, ROUNDS))}
+            med = {s: statistics.median(v) for s, v in ts.items()}
+            sp1 = max(ts[1]) - min(ts[1])
+            best = min(med, key=med.get)
+            verdict = "-"
+            if plan > 1:
+                verdict = "gain" if med[1] - med[plan] > sp1 else "MISS: planned split not faster beyond the spread"
+            elif med[1] - med[best] > sp1:
+                verdict = "left: S=%d is %.1f us faster" % (best, med[1] - med[best])
+            if verdict.startswith(("MISS", "left")):
+                misses.append((key, verdict))
+            tot[0] += med[1] * c["n"]
+            tot[1] += med[plan] * c["n"]
+            p("%7d %5d %6d %4d %3d %3s %5d %4d %4d |" % (M, N, K, taps, stride, "x" if ups else "", c["n"], tile, T)
+              + "".join(" %7s" % ("%.1f" % med[s] if s in med else "") for s in KSPLITS)
+              + " | [%7.1f .. %7.1f] | %4d %7.1f [%7.1f .. %7.1f] %s" % (min(ts[1]), max(ts[1]), plan, med[plan], min(ts[plan]), max(ts[plan]), verdict))
+            del graphs
+        p("%s: sum over the call (shape time x calls): un-split %.1f us, planned %.1f us (%.1f us less); rows the rule misses or leaves: %d"
+          % (name, tot[0], tot[1], tot[0] - tot[1], len(misses)))
+        for key, v in misses:
+            p("    %s: %s" % (key, v))
+    calls.clear()
+    gc.collect()
+    torch.cuda.empty_cache()
+    if whole:
+        qnn.set_weight_only_mfma16(True)
+        rounds = 9
+        for dt in dtypes:
+            name = str(dt).replace("torch.", "")
+            qnn = qnn.to(dt)
+            xd, cd = x.to(dt), ctx.to(dt)
+            qnn.set_attention_mfma16(dt != torch.float32)
+            qnn.set_attention_mfma16_fp32(dt == torch.float32)
+            graphs, ys = [], []
+            try:
+                for ks in (1, None):
+                    ops.WQ16_KSPLIT = ks
+                    with torch.no_grad():
+                        ys.append(qnn(xd, t, cd)[0].double())
+                        graphs.append(graph_of(lambda: qnn(xd, t, cd)))
+            finally:
+                ops.WQ16_KSPLIT = None
+            ts = _rounds_ms(graphs, ITERS, rounds)
+            med = [statistics.median(v) for v in ts]
+            p("%s state, whole UNet call (CFG pair, set_weight_only_mfma16 and the attention switch on; graph replay, %d alternating rounds of "
+              "%d calls), ms per call:" % (name, rounds, ITERS))
+            p("    WQ16_KSPLIT = 1:    %s" % " ".join("%.3f" % v for v in ts[0]))
+            p("    WQ16_KSPLIT = None: %s" % " ".join("%.3f" % v for v in ts[1]))
+            p("    medians %.3f -> %.3f ms (%.3f ms less); spread of the un-split route (max - min) %.3f ms; the plan lower in %d of %d rounds; "
+              "rel-L2 between the outputs %.2e" % (med[0], med[1], med[0] - med[1], max(ts[0]) - min(ts[0]), sum(b < a_ for a_, b in zip(*ts)),
+                                                   rounds, float((ys[1] - ys[0]).norm() / ys[0].norm())))
+            del graphs
+            gc.collect()
+            torch.cuda.empty_cache()
+    del qnn
+    gc.collect()
+    torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--arch", default="sd")
@@ -294,6 +409,9 @@ if __name__ == "__main__":
     ap.add_argument("--fused", action="store_true",
                     help="measure QuantModel.set_weight_only_fused off against on instead (e.g. --bits 4 --dtypes bfloat16 float32 "
                          "--out profiles/r20_weight_only_fused.txt)")
+    ap.add_argument("--ksplit", action="store_true",
+                    help="measure the K split of the matrix-core route instead: the forced-S sweep per shape and the whole call with "
+                         "ops.WQ16_KSPLIT = 1 against the plan (e.g. --bits 4 --dtypes bfloat16 float32 --out profiles/r25_weight_only_ksplit.txt)")
     ap.add_argument("--commit", default="unknown", help="stamped into the report")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     args = ap.parse_args()
@@ -304,4 +422,4 @@ if __name__ == "__main__":
         print(head, flush=True)
         print(head, file=fh)
         for b in args.bits:
-            (run_fused if args.fused else run)(args.arch, b, args.res, args.batch, [DTYPES[d] for d in args.dtypes], not args.no_whole, fh)
+            (run_ksplit if args.ksplit else run_fused if args.fused else run)(args.arch, b, args.res, args.batch, [DTYPES[d] for d in args.dtypes], not args.no_whole, fh)
