@@ -72,6 +72,10 @@ SIGNATURES = {
     "dgq_gemm_mxw8": [_vp, _vp, _vp],
     "dgq_gemm_mxw8_splitk": [_vp, _vp, _i, _vp, ctypes.c_size_t, _vp],
     "dgq_gemm_mx_workspace_bytes": [_i, _i, _i],
+    "dgq_quant_act_mx4": [_vp, _vp, _vp],
+    "dgq_dequant_act_mx4": [_vp, _vp, _i, _i64, _i, _vp, _i, _vp],
+    "dgq_gemm_mx4": [_vp, _vp, _vp],
+    "dgq_gemm_mx4_splitk": [_vp, _vp, _i, _vp, ctypes.c_size_t, _vp],
     "dgq_gemm_wxa8_batch": [_i, _vp, _vp],
     "dgq_adaround_soft_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
     "dgq_adaround_soft_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
@@ -152,6 +156,16 @@ class ActMxInt8Out(ctypes.Structure):
 
 class GemmMxInt8(ctypes.Structure):
     """dgq_gemm_mxint8_t of include/dgq_hip.h"""
+    _fields_ = GemmMx6._fields_
+
+
+class ActMx4Out(ctypes.Structure):
+    """dgq_act_mx4_out_t of include/dgq_hip.h"""
+    _fields_ = ActMx6Out._fields_
+
+
+class GemmMx4(ctypes.Structure):
+    """dgq_gemm_mx4_t of include/dgq_hip.h"""
     _fields_ = GemmMx6._fields_
 
 

@@ -51,11 +51,13 @@ def parse_args(argv=None):
     p.add_argument("--aq_real_time_block", type=int, default=0,
                    help="with --aq_real_time: 32 = one pair per row and block of 32 consecutive channels (dgq_quant_act_block + "
                         "dgq_gemm_blockq); 0 = one pair per row")
-    p.add_argument("--aq_real_time_format", default="int", choices=("int", "mxfp6", "mxint8"),
+    p.add_argument("--aq_real_time_format", default="int", choices=("int", "mxfp6", "mxint8", "mxfp4"),
                    help="with --aq_real_time --aq_real_time_block 32 and 6 activation bits: mxfp6 = every block one power-of-two scale and "
                         "32 FP6 E2M3 codes on the block-scaled matrix cores (dgq_quant_act_mx6 + dgq_gemm_mx6; W4 layers, W4A6); with 8 "
                         "activation bits: mxint8 = every block one power-of-two scale and 32 int8 codes, run as two E2M3 terms on the same "
-                        "cores (dgq_quant_act_mxint8 + dgq_gemm_mxint8; W4 layers, W4A8)")
+                        "cores (dgq_quant_act_mxint8 + dgq_gemm_mxint8; W4 layers, W4A8); with 4 activation bits: mxfp4 = every block one "
+                        "power-of-two scale and 32 FP4 E2M1 codes, the FP4 operand of the same cores against the FP6 weights "
+                        "(dgq_quant_act_mx4 + dgq_gemm_mx4; W4 layers, W4A4)")
     p.add_argument("--aq_real_time_mx_w8", action="store_true",
                    help="with --aq_real_time_format mxfp6 / mxint8: W8 layers (integer zero points) take the MX format too, their weight "
                         "as two FP6 E2M3 planes (dgq_pack_w_mx6x2 + dgq_gemm_mxw8; W8A6 / W8A8) instead of the int8 block mode")
@@ -101,6 +103,9 @@ def main(argv=None):
     if opt.aq_real_time_format == "mxint8" and not (opt.use_aq and opt.aq_real_time and opt.aq_real_time_block == 32 and opt.aq == 8):
         raise SystemExit("--aq_real_time_format mxint8 is a format of the real-time block mode at 8 activation bits: it needs --use_aq "
                          "--aq_real_time --aq_real_time_block 32 and --aq 8")
+    if opt.aq_real_time_format == "mxfp4" and not (opt.use_aq and opt.aq_real_time and opt.aq_real_time_block == 32 and opt.aq == 4):
+        raise SystemExit("--aq_real_time_format mxfp4 is a format of the real-time block mode at 4 activation bits: it needs --use_aq "
+                         "--aq_real_time --aq_real_time_block 32 and --aq 4")
     if opt.aq_real_time_mx_w8 and opt.aq_real_time_format not in ("mxfp6", "mxint8"):
         raise SystemExit("--aq_real_time_mx_w8 extends an MX format to the W8 layers: it needs --aq_real_time_format mxfp6 or mxint8")
     logging.basicConfig(level=logging.INFO)

@@ -411,24 +411,30 @@ class BlockActBinding(ActBinding):
         self.vc = pw.vc()
 
 
+#: activation bits of the MX formats of a MxActBinding
+MX_FORMAT_BITS = {"mxfp6": 6, "mxint8": 8, "mxfp4": 4}
+
+
 class MxActBinding(BlockActBinding):
     """The binding of a real-time MXFP6 activation quantizer (UniformAffineQuantizer(real_time=True, real_time_block=32,
     real_time_format="mxfp6")) on a layer whose weight is exact in FP6 E2M3 (PackedWeight.mx6_eligible): the MX weight image, bias and δw —
     no tables, no timestep slots, one binding per layer.  The routes of a block binding run it as dgq_quant_act_mx6 on the layer INPUT
     (once per row / pixel: 24 code bytes and one E8M0 scale byte per 32-channel block) + dgq_gemm_mx6.  ``fmt`` carries the MX format:
     real_time_format="mxint8" (8 bits) is the same binding on the MXINT8 entries.  ``w_bits=8`` (real_time_mx_w8=True on a W8 layer,
-    PackedWeight.mxw8_eligible) binds the two-plane W8 image instead: the same quantisers + dgq_gemm_mxw8."""
+    PackedWeight.mxw8_eligible) binds the two-plane W8 image instead: the same quantisers + dgq_gemm_mxw8.  real_time_format="mxfp4"
+    (4 bits) is the same binding and weight image on the MXFP4 entries (W4 only)."""
 
     mx = True
 
     def __init__(self, pw: PackedWeight, fmt: str = "mxfp6", *, w_bits: int = 4):
         """fmt "mxint8" (real_time_format="mxint8", 8 bits): the same weight image and eligibility under MXINT8 blocks — 48 code bytes
         (two E2M3 planes of the int8 code) and one scale byte per block, dgq_quant_act_mxint8 + dgq_gemm_mxint8.  w_bits 8: the image of
-        PackedWeight.mx6x2 under either format (dgq_gemm_mxw8)"""
+        PackedWeight.mx6x2 under either format (dgq_gemm_mxw8).  fmt "mxfp4" (real_time_format="mxfp4", 4 bits): the same weight image
+        and eligibility under MXFP4 blocks — 16 code bytes and one scale byte per block, dgq_quant_act_mx4 + dgq_gemm_mx4; W4 only"""
         assert pw.C % 32 == 0, "real-time MX quantizer: C % 32 == 0"
-        assert fmt in ("mxfp6", "mxint8") and w_bits in (4, 8)
+        assert fmt in MX_FORMAT_BITS and w_bits in (4, 8) and not (fmt == "mxfp4" and w_bits == 8)
         self.fmt, self.w_bits = fmt, w_bits
-        self.mode, self.abits, self.offset = "block", 8 if fmt == "mxint8" else 6, 0.0
+        self.mode, self.abits, self.offset = "block", MX_FORMAT_BITS[fmt], 0.0
         self.pw = pw
         self.wpacked, self.Kp = pw.mx6x2() if w_bits == 8 else pw.mx6()
         self.wfrag = None
@@ -1094,6 +1100,34 @@ def gemm_mxint8(q, geom, ab: "MxActBinding", out_dtype, out=None, extra=None, up
     return _block_gemm_launch("dgq_gemm_mxint8", k, q, geom, ab, out_dtype, out, extra, ups, ksplit=ksplit, w_bits=4)
 
 
+def quant_act_mx4(x_cl: torch.Tensor, geom, pre=None, ln=None, ups=False, lds=None):
+    """dgq_quant_act_mx4 on the layer INPUT x_cl (as quant_act_mx6): one launch.  Returns (codes uint8 [rows][C/32][16] = a block's 32
+    FP4 codes, element j at bits 4j .. 4j + 3, scale uint8 [rows][lds] = E + 127 per 32-channel block)."""
+    def outputs(rows, C, lds, dev):
+        codes = torch.empty((rows, C // 32, 16), dtype=torch.uint8, device=dev)
+        scale = torch.empty((rows, lds), dtype=torch.uint8, device=dev)
+        o = _lib.ActMx4Out()
+        o.codes, o.scale, o.lds = codes.data_ptr(), scale.data_ptr(), lds
+        return o, (codes, scale)
+    return _block_quant_launch("dgq_quant_act_mx4", x_cl, geom, 4, pre, ln, ups, lds, outputs)
+
+
+def dequant_act_mx4(codes, scale, out):
+    """out [rows][C] = x̂ from quant_act_mx4's codes and scales (dgq_dequant_act_mx4)"""
+    rows, C = codes.shape[0], codes.shape[1] * 32
+    _lib_call("dgq_dequant_act_mx4", _lib.ptr(codes), _lib.ptr(scale), scale.shape[1], rows, C, _lib.ptr(out), _lib.DTYPE_CODE[out.dtype],
+              _lib.stream())
+    return out
+
+
+def gemm_mx4(q, geom, ab: "MxActBinding", out_dtype, out=None, extra=None, ups=False, ksplit=1):
+    """One dgq_gemm_mx4 launch on q = quant_act_mx4(...) of the layer input against the MXFP6 weight image of ab; geom, ksplit
+    (dgq_gemm_mx4_splitk) and the result as for gemm_mx6."""
+    k = _lib.GemmMx4()
+    k.scale, k.lds = q[1].data_ptr(), q[1].shape[1]
+    return _block_gemm_launch("dgq_gemm_mx4", k, q, geom, ab, out_dtype, out, extra, ups, ksplit=ksplit, w_bits=4)
+
+
 def gemm_mxw8(q, geom, ab: "MxActBinding", out_dtype, out=None, extra=None, ups=False, ksplit=1):
     """One dgq_gemm_mxw8 launch on q = quant_act_mx6(...) or quant_act_mxint8(...) (ab.fmt) of the layer input against the two-plane W8
     image of ab (MxActBinding(pw, fmt, w_bits=8)); geom, ksplit and the result as for gemm_mx6."""
@@ -1105,12 +1139,13 @@ def gemm_mxw8(q, geom, ab: "MxActBinding", out_dtype, out=None, extra=None, ups=
 def _block_quant(ab, x_cl, geom, pre=None, ln=None, ups=False, pad_k=False):
     """the input of a block binding quantised by its format's entry; pad_k: table / scale entries up to Kp/32 (Linear layers)"""
     if ab.mx:
-        return (quant_act_mxint8 if ab.fmt == "mxint8" else quant_act_mx6)(x_cl, geom, pre, ln, ups, lds=ab.Kp // 32 if pad_k else None)
+        quant = {"mxfp6": quant_act_mx6, "mxint8": quant_act_mxint8, "mxfp4": quant_act_mx4}[ab.fmt]
+        return quant(x_cl, geom, pre, ln, ups, lds=ab.Kp // 32 if pad_k else None)
     return quant_act_block(x_cl, geom, ab.abits, pre, ln, ups, ldt=ab.Kp // 32 if pad_k else None)
 
 
 #: the K split of the MX layers (quant_linear, quant_conv2d, the batched Linear path): None = the library's plan per shape
-#: (dgq_gemm_mx_plan_splits), 1 = never, an int = forced — what _block_gemm hands to gemm_mx6 / gemm_mxint8 / gemm_mxw8 as ``ksplit``
+#: (dgq_gemm_mx_plan_splits), 1 = never, an int = forced — what _block_gemm hands to gemm_mx6 / gemm_mxint8 / gemm_mx4 / gemm_mxw8 as ``ksplit``
 MX_KSPLIT = None
 
 
@@ -1123,7 +1158,7 @@ def _block_gemm(ab, q, geom, out_dtype, out=None, extra=None, ups=False):
         M = B * ((H + 2 * pad - kh) // stride + 1) * ((W + 2 * pad - kw) // stride + 1)
         if _lib.load().dgq_gemm_mx_plan_splits(M, ab.pw.N, ab.Kp, WORKSPACE_BYTES) == 1:
             ksplit = 1
-    gemm = gemm_mxw8 if ab.w_bits == 8 else gemm_mxint8 if ab.fmt == "mxint8" else gemm_mx6
+    gemm = gemm_mxw8 if ab.w_bits == 8 else {"mxfp6": gemm_mx6, "mxint8": gemm_mxint8, "mxfp4": gemm_mx4}[ab.fmt]
     return gemm(q, geom, ab, out_dtype, out=out, extra=extra, ups=ups, ksplit=ksplit)
 
 

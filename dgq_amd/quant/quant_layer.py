@@ -227,6 +227,54 @@ def mx6_unpack(packed: torch.Tensor):
     return torch.stack([(w >> (6 * j)) & 63 for j in range(4)], dim=-1).to(torch.uint8).view(R, -1)
 
 
+#: E2M1 magnitudes by 3-bit code (exponent << 1 | mantissa): the subnormal m/2, then (1 + m/2)·2^(e−1)
+E2M1_MAGNITUDES = tuple(m / 2.0 if e == 0 else (1.0 + m / 2.0) * 2.0 ** (e - 1) for e in range(4) for m in range(2))
+
+
+def mx4_block(rows: torch.Tensor):
+    """The MXFP4 statement dgq_quant_act_mx4 reproduces bit for bit (``real_time_format="mxfp4"``): rows [R][C] fp32 (C % 32 == 0, finite,
+    behind any folded prologue), every 32 consecutive channels one block.  With amax = max |x′| of the block, E = floor(log2 amax) − 2
+    — the OCP MX rule for E2M1 (emax 2, as E2M3), read off the exponent field of amax — clamped to [−127, 127], −127 for a zero or
+    subnormal amax; v = x′·2^−E (an exact scaling, |v| < 8) is rounded to nearest, ties to the even code, onto the E2M1 grid
+    {0, 0.5, 1, 1.5, 2, 3, 4, 6} (steps 0.5 below 2, 1 below 4, 2 above: in each range the even multiples of the step are the even codes)
+    and saturates at ±6; a zero magnitude is the code +0.  Returns (codes uint8 [R][C] = sign << 3 | exponent << 1 | mantissa, scale
+    uint8 [R][C/32] = E + 127, x̂ fp32 [R][C] = value(code)·2^E)."""
+    x = rows.detach().float()
+    R, C = x.shape
+    assert C % REAL_TIME_BLOCK == 0
+    xb = x.view(R, C // REAL_TIME_BLOCK, REAL_TIME_BLOCK)
+    amax = xb.abs().amax(dim=2)
+    field = (amax.contiguous().view(torch.int32) >> 23) & 0xFF              # 0 for zero and subnormal amax
+    E = torch.clamp(field - 129, min=-127)                                     # (finite amax: at most 125)
+    inv = torch.ldexp(torch.ones_like(amax), -E)                               # 2^−E, a normal float
+    v = xb * inv[:, :, None]
+    a = v.abs()
+    step = torch.where(a < 2.0, torch.full_like(a, 0.5), torch.where(a < 4.0, torch.full_like(a, 1.0), torch.full_like(a, 2.0)))
+    q = torch.clamp(torch.round(a / step) * step, max=6.0)                     # torch.round: half to even; a / step is exact
+    qe = torch.floor(torch.log2(torch.clamp(q, min=1.0))).to(torch.int32)      # 0, 1, 2 for the normal ranges (exact at powers of two)
+    mag = torch.where(q < 1.0, (q * 2.0).to(torch.int32), ((qe + 1) << 1) | ((q / torch.ldexp(torch.ones_like(q), qe) - 1.0) * 2.0).to(torch.int32))
+    sign = torch.where((v < 0) & (mag > 0), 8, 0).to(torch.int32)
+    codes = (mag | sign).to(torch.uint8).view(R, C)
+    xhat = (torch.where(v < 0, -q, q) * torch.ldexp(torch.ones_like(amax), E)[:, :, None]).view(R, C)
+    return codes, (E + 127).to(torch.uint8), xhat
+
+
+def mx4_pack(codes: torch.Tensor):
+    """4-bit codes [R][C] (uint8) -> [R][C/32][16] bytes: element j of a block at bits 4j .. 4j + 3 of its 128-bit little-endian string
+    (the even element in a byte's low nibble) — the FP4 operand image, as the instruction reads it from a lane's first four registers
+    (pinned by the one-hot tests of tests/test_gpu_realtime_mxfp4.py)"""
+    R, C = codes.shape
+    c = codes.view(R, C // 2, 2)
+    return (c[..., 0] | (c[..., 1] << 4)).view(R, C // REAL_TIME_BLOCK, 16)
+
+
+def mx4_unpack(packed: torch.Tensor):
+    """inverse of ``mx4_pack``: [R][C/32][16] bytes -> codes uint8 [R][C]"""
+    R = packed.shape[0]
+    b = packed.reshape(R, -1)
+    return torch.stack([b & 15, b >> 4], dim=-1).view(R, -1)
+
+
 def mxint8_block(rows: torch.Tensor):
     """The MXINT8 statement dgq_quant_act_mxint8 reproduces bit for bit (``real_time_format="mxint8"``): rows [R][C] fp32 (C % 32 == 0,
     finite, behind any folded prologue), every 32 consecutive channels one block.  With amax = max |x′| of the block, E = floor(log2 amax)
@@ -341,7 +389,12 @@ class UniformAffineQuantizer(nn.Module):
     (dgq_quant_act_mxint8 + dgq_gemm_mxint8).  The same layers take it as take MXFP6; every other layer runs as with
     ``real_time_block=32`` alone.
 
-    ``real_time_mx_w8=True`` (with either MX format; opt-in): W8 layers with integer zero points and C % 32 == 0 take the MX format too,
+    ``real_time_format="mxfp4"`` (with ``real_time_block=32`` and 4 bits): the block is an OCP MXFP4 block — one power-of-two scale and
+    32 FP4 E2M1 codes (``mx4_block``), the FP4 operand of the same instruction against the FP6 weights (dgq_quant_act_mx4 +
+    dgq_gemm_mx4).  The same layers take it as take MXFP6; every other layer runs as with ``real_time_block=32`` alone at 4 bits.
+    ``real_time_mx_w8`` is not available under it.
+
+    ``real_time_mx_w8=True`` (with the MXFP6 or MXINT8 format; opt-in): W8 layers with integer zero points and C % 32 == 0 take the MX format too,
     their weight as two E2M3 planes (``mxw8_split``; dgq_pack_w_mx6x2 + dgq_gemm_mxw8) — without it they run as with
     ``real_time_block=32`` alone."""
 
@@ -357,12 +410,14 @@ class UniformAffineQuantizer(nn.Module):
         if real_time_block not in (0, REAL_TIME_BLOCK) or (real_time_block and not real_time):
             raise ValueError("real_time_block is 0 (one pair per row) or %d (one pair per row and block of %d consecutive channels), and a "
                              "granularity of real_time=True" % (REAL_TIME_BLOCK, REAL_TIME_BLOCK))
-        if real_time_format not in ("int", "mxfp6", "mxint8"):
-            raise ValueError("real_time_format is \"int\", \"mxfp6\" or \"mxint8\", not %r" % (real_time_format,))
+        if real_time_format not in ("int", "mxfp6", "mxint8", "mxfp4"):
+            raise ValueError("real_time_format is \"int\", \"mxfp6\", \"mxint8\" or \"mxfp4\", not %r" % (real_time_format,))
         if real_time_format == "mxfp6" and not (real_time and real_time_block == REAL_TIME_BLOCK and bits == 6):
             raise ValueError("real_time_format=\"mxfp6\" is a format of real_time=True with real_time_block=%d and bits=6" % REAL_TIME_BLOCK)
         if real_time_format == "mxint8" and not (real_time and real_time_block == REAL_TIME_BLOCK and bits == 8):
             raise ValueError("real_time_format=\"mxint8\" is a format of real_time=True with real_time_block=%d and bits=8" % REAL_TIME_BLOCK)
+        if real_time_format == "mxfp4" and not (real_time and real_time_block == REAL_TIME_BLOCK and bits == 4):
+            raise ValueError("real_time_format=\"mxfp4\" is a format of real_time=True with real_time_block=%d and bits=4" % REAL_TIME_BLOCK)
         if real_time_mx_w8 and real_time_format not in ("mxfp6", "mxint8"):
             raise ValueError("real_time_mx_w8=True extends real_time_format=\"mxfp6\" / \"mxint8\" to W8 layers: it needs one of them")
         self.real_time_mx_w8 = bool(real_time_mx_w8)
@@ -521,6 +576,11 @@ class UniformAffineQuantizer(nn.Module):
                     codes, scale = ops.quant_act_mxint8(x2d, (x2d.shape[0], 1, 1, x2d.shape[1], 1, 1, 1, 0))
                     out = torch.empty_like(xc)
                     ops.dequant_act_mxint8(codes, scale, out.view(x2d.shape))
+                    return out
+                if self.real_time_format == "mxfp4":
+                    codes, scale = ops.quant_act_mx4(x2d, (x2d.shape[0], 1, 1, x2d.shape[1], 1, 1, 1, 0))
+                    out = torch.empty_like(xc)
+                    ops.dequant_act_mx4(codes, scale, out.view(x2d.shape))
                     return out
                 codes, table, _rho = ops.quant_act_block(x2d, (x2d.shape[0], 1, 1, x2d.shape[1], 1, 1, 1, 0), self.bits)
                 out = torch.empty_like(xc)
@@ -753,7 +813,7 @@ class QuantLayer(nn.Module):
         if self.aqtizer.real_time:                # no tables, no slots: one natural-order binding, its row tables made per call
             if "real_time" not in self._bindings:
                 # block granularity where the input channels split into whole 32-blocks; the per-row mode otherwise
-                # (MXFP6 / MXINT8 blocks where the format asks for them and the weight is exact in E2M3 — W4 in one plane; with
+                # (MXFP6 / MXINT8 / MXFP4 blocks where the format asks for them and the weight is exact in E2M3 — W4 in one plane; with
                 # real_time_mx_w8, W8 in two)
                 blk = self.aqtizer.real_time_block
                 whole = blk and self.in_channels % blk == 0
@@ -762,6 +822,8 @@ class QuantLayer(nn.Module):
                     self._bindings["real_time"] = ops.MxActBinding(pw)
                 elif whole and fmt == "mxint8" and pw.mx6_eligible:
                     self._bindings["real_time"] = ops.MxActBinding(pw, "mxint8")
+                elif whole and fmt == "mxfp4" and pw.mx6_eligible:
+                    self._bindings["real_time"] = ops.MxActBinding(pw, "mxfp4")
                 elif whole and self.aqtizer.real_time_mx_w8 and pw.bits == 8 and pw.mxw8_eligible:
                     self._bindings["real_time"] = ops.MxActBinding(pw, fmt, w_bits=8)
                 else:

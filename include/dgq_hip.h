@@ -54,7 +54,9 @@ extern "C" {
  *        dgq_gemm_mxint8 with dgq_act_mxint8_out_t and dgq_gemm_mxint8_t; their K split (dgq_gemm_mx6_splitk, dgq_gemm_mxint8_splitk,
  *        dgq_gemm_mx_plan_splits, dgq_gemm_mx_workspace_bytes); W8 weights under both MX formats, dgq_pack_w_mx6x2 / dgq_gemm_mxw8 /
  *        dgq_gemm_mxw8_splitk with dgq_gemm_mxw8_t; the K split of the weight-only matrix-core layer (dgq_conv2d_wq_mfma16_splitk,
- *        dgq_conv2d_wq_mfma16_plan_splits, dgq_conv2d_wq_mfma16_workspace_bytes) — entries added only, the revision stays 123 */
+ *        dgq_conv2d_wq_mfma16_plan_splits, dgq_conv2d_wq_mfma16_workspace_bytes); the real-time MXFP4 mode, dgq_quant_act_mx4 /
+ *        dgq_dequant_act_mx4 / dgq_gemm_mx4 / dgq_gemm_mx4_splitk with dgq_act_mx4_out_t and dgq_gemm_mx4_t — entries added only, the
+ *        revision stays 123 */
 #define DGQ_ABI_VERSION 123
 int dgq_version(void);
 const char* dgq_last_error(void);
@@ -556,6 +558,36 @@ typedef struct dgq_gemm_mxw8 {
 } dgq_gemm_mxw8_t;
 int dgq_gemm_mxw8(const dgq_gemm_args_t* g, const dgq_gemm_mxw8_t* mx, void* stream);
 int dgq_gemm_mxw8_splitk(const dgq_gemm_args_t* g, const dgq_gemm_mxw8_t* mx, int splits, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- real-time MXFP4 activations on the block-scaled matrix cores (W4A4; a mode of this library) ---------------------------------------
+ * Every block of DGQ_KCHUNK = 32 consecutive channels of every input row is an OCP MXFP4 block: ONE power-of-two scale 2^E and 32 FP4
+ * E2M1 codes (sign << 3 | exponent << 1 | mantissa; magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6).  With amax = max |x′| of the block:
+ * E = floor(log2 amax) − 2 (the exponent field of amax; the OCP MX rule with the element emax 2), clamped to [−127, 127], −127 for a zero
+ * or subnormal amax; code = x′·2^−E rounded to nearest, ties to the even code, saturating at ±6 (a zero magnitude is stored +0);
+ * x̂ = code·2^E.  The statement is dgq_amd/quant/quant_layer.py mx4_block.
+ * dgq_quant_act_mx4: `in` is read exactly as by dgq_quant_act_mx6.  ONE launch, no atomics, capture-safe:
+ *   codes [rows][C/32][16 bytes], 16-byte aligned: a block's codes as a 128-bit little-endian string, element j at bits 4j .. 4j + 3
+ *         (quant_layer.mx4_pack) — one 16-byte store per block;
+ *   scale [rows][lds] E8M0 bytes E + 127, lds >= C/32; entries C/32 .. lds − 1 are written 127.
+ * dgq_dequant_act_mx4: y [rows][C] (y_dtype) = x̂ from such codes and scales (one rounding into a 16-bit y).
+ * dgq_gemm_mx4: y[m,n] = gamma[n] + alpha[n]·Σ_c 2^(E[m,c]+1)·Σ_{k∈c} a4[m,k]·w6[n,k]; every K step one block-scaled MFMA with the
+ * activations as its FP4 operand under the block's scale byte and the weights as its FP6 E2M3 operand — g->wpacked is
+ * dgq_pack_w_mx6's image, unchanged — under the constant byte 128; ONE fp32 accumulator over the whole K.  Every product is exact; only
+ * the fp32 accumulation rounds.  Arguments, rows, chunks, taps, ups, the Linear case and the epilogue forms as for dgq_gemm_mx6 (codes =
+ * this quantiser's; a tap outside the image contributes exactly 0; extra.conv and extra.act must be NULL).
+ * dgq_gemm_mx4_splitk: its K split, as dgq_gemm_mx6_splitk (same partial layout, combine kernel and plan: dgq_gemm_mx_plan_splits /
+ * dgq_gemm_mx_workspace_bytes). */
+typedef struct dgq_act_mx4_out {
+    uint8_t* codes; uint8_t* scale; int lds;
+} dgq_act_mx4_out_t;
+int dgq_quant_act_mx4(const dgq_quant_act_args_t* in, const dgq_act_mx4_out_t* out, void* stream);
+int dgq_dequant_act_mx4(const uint8_t* codes, const uint8_t* scale, int lds, int64_t rows, int C, void* y, int y_dtype, void* stream);
+typedef struct dgq_gemm_mx4 {
+    const uint8_t* scale; int lds;    /* dgq_act_mx4_out_t.scale / lds */
+    int B, H, W, C, kh, kw, stride, pad, ups;
+} dgq_gemm_mx4_t;
+int dgq_gemm_mx4(const dgq_gemm_args_t* g, const dgq_gemm_mx4_t* mx, void* stream);
+int dgq_gemm_mx4_splitk(const dgq_gemm_args_t* g, const dgq_gemm_mx4_t* mx, int splits, void* workspace, size_t workspace_bytes, void* stream);
 /* Small tile grids are split along K (deterministic: fp32 partial slabs [S][M][N] in the caller's `workspace`,
  * summed in a fixed order by a second kernel). dgq_gemm_workspace_bytes returns what the preferred split of a
  * shape needs; with workspace == NULL (or too small) fewer / no splits are used — results do not depend on it

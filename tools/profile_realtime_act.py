@@ -290,7 +290,7 @@ def build_rt_model(torch, arch, fmt, abits, steps_cfg, batch, res, dev, use_aq=T
         aq["real_time_mx_w8"] = True
     if fmt != "row":
         aq["real_time_block"] = 32
-    if fmt in ("mxfp6", "mxint8"):
+    if fmt in ("mxfp6", "mxint8", "mxfp4"):
         aq["real_time_format"] = fmt
     qnn = get_qmodel(arch, types.SimpleNamespace(unet=unet), path, wq, use_aq, aq, sm, False, steps_cfg, False, device=dev)
     qnn = qnn.float().to(dev)
