@@ -58,6 +58,9 @@ SIGNATURES = {
     "dgq_quant_act_block": [_vp, _vp, _vp],
     "dgq_dequant_act_block": [_vp, _vp, _i, _i64, _i, _vp, _i, _vp],
     "dgq_gemm_blockq": [_vp, _vp, _vp],
+    "dgq_gemm_blockq_splitk": [_vp, _vp, _i, _vp, ctypes.c_size_t, _vp],
+    "dgq_gemm_blockq_plan_splits": [_i, _i, _i, _i, ctypes.c_size_t],
+    "dgq_gemm_blockq_workspace_bytes": [_i, _i, _i, _i],
     "dgq_quant_act_mx6": [_vp, _vp, _vp],
     "dgq_dequant_act_mx6": [_vp, _vp, _i, _i64, _i, _vp, _i, _vp],
     "dgq_pack_w_mx6": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],

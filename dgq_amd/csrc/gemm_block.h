@@ -63,8 +63,7 @@ __device__ __forceinline__ void block_store(const GemmParams& p, uint8_t* smem, 
     DGQ_STAMP(10); DGQ_STAMP_REAL(11);
 }
 
-// ---- The K split of the block-scaled formats (gemm_mx6.hip, gemm_mxint8.hip; the combine and the plan: gemm_mx_split.hip).  Split s =
-// blockIdx.z of a tile walks K tiles [s·tps, min((s + 1)·tps, nkt)) and leaves, instead of block_store, each wave's raw accumulator in
+// ---- The K split of the family (gemm_mx*.hip, gemm_blockq.hip; the combine and the plans: gemm_mx_split.hip).  Split s = blockIdx.z of a tile walks K tiles [s·tps, min((s + 1)·tps, nkt)) and leaves, instead of block_store, each wave's raw accumulator in
 // the caller's workspace in the accumulator's own order, [split][tile_m][tile_n][wave][reg / 4][lane] as float4: 16-byte stores, a
 // wave's 64 lanes on 1 KiB in a row, no LDS transposition, no epilogue.  32 KiB per tile and split, ragged tiles whole; the two K waves
 // of a tile stay apart (2S partials per output tile).  The combine — a launch of its own on the tile grid, the kernel boundary is the
@@ -84,9 +83,12 @@ __device__ __forceinline__ void block_store_partial(const BlockSplit& z, const B
     for (int j = 0; j < 4; ++j) dst[64 * j] = make_float4(acc[4 * j], acc[4 * j + 1], acc[4 * j + 2], acc[4 * j + 3]);
 }
 
-// gemm_mx_split.hip: the plan for nkt K tiles (1 = un-split) and the combine launch behind a split one
+// gemm_mx_split.hip: the plans for nkt K tiles (1 = un-split; the MX formats', and gemm_blockq.hip's own) and the combine launch behind
+// a split one.  zp: the gather of a format with zero-point terms — the combine then forms R[m] over the in-image taps and reads zw[n]
+// as the un-split kernel does in front of its K loop; NULL (the MX formats): R = 0, zw = 0.
 int block_split_plan(int M, int N, int nkt, size_t workspace_bytes);
-int block_combine_launch(const char* who, const GemmParams& p, const BlockSplit& z, int splits, int y_dtype, hipStream_t st);
+int blockq_split_plan(int M, int N, int nkt, int w_bits, size_t workspace_bytes);
+int block_combine_launch(const char* who, const GemmParams& p, const BlockSplit& z, int splits, int y_dtype, hipStream_t st, const BlockGather* zp = nullptr);
 
 // The shared part of a block entry: checks of the problem, the geometry and the extras; GemmParams and the gather.  zero_point: the
 // format has zero-point terms (row sums, zw, offset); without, the epilogue runs with R = 0 and zw = 0 and the three are not read.
@@ -137,12 +139,13 @@ static int block_gemm_launch(const char* who, const GemmParams& p, const BlockGa
     return dgq_launch_status(who);
 }
 
-// The launch of a *_splitk entry.  splits: 0 = the plan's choice, >= 1 forced; either is clamped to the K tiles and to what the
-// workspace holds (none: 1), and no split is empty.  One split is the un-split kernel.  Kernel::split = the split instance taking
-// (GemmParams, BlockGather, Operand, BlockSplit): it has no epilogue, hence no output dtype.
+// The launch of a *_splitk entry.  splits: 0 = the MX plan's choice (a format with a plan of its own resolves 0 itself), >= 1 forced;
+// either is clamped to the K tiles and to what the workspace holds (none: 1), and no split is empty.  One split is the un-split kernel.
+// Kernel::split = the split instance taking (GemmParams, BlockGather, Operand, BlockSplit): it has no epilogue, hence no output dtype.
+// zero_point: the combine applies the format's zero-point term (block_combine_launch).
 template <typename Kernel, typename Operand>
 static int block_gemm_launch_split(const char* who, const GemmParams& p, const BlockGather& q, const Operand& o, int y_dtype, int splits,
-                                   void* workspace, size_t workspace_bytes, hipStream_t st) {
+                                   void* workspace, size_t workspace_bytes, hipStream_t st, bool zero_point = false) {
     DGQ_CHECK_ARG(splits >= 0, "%s: splits=%d", who, splits);
     DGQ_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", who);
     DGQ_CHECK_ARG(y_dtype == DGQ_F32 || y_dtype == DGQ_F16 || y_dtype == DGQ_BF16, "%s: unknown y dtype %d", who, y_dtype);
@@ -157,5 +160,5 @@ static int block_gemm_launch_split(const char* who, const GemmParams& p, const B
     s = (nkt + z.tps - 1) / z.tps;                          // no empty split
     if (s == 1) return block_gemm_launch<Kernel>(who, p, q, o, y_dtype, st);
     hipLaunchKernelGGL(Kernel::split, dim3(tiles.x, tiles.y, s), dim3(BLK_NT), 0, st, p, q, o, z);
-    return block_combine_launch(who, p, z, s, y_dtype, st);
+    return block_combine_launch(who, p, z, s, y_dtype, st, zero_point ? &q : nullptr);
 }

@@ -18,8 +18,9 @@
 // chunk per wave (against 4-chunk tiles: the same times — the loop is bound by the per-chunk body, not by the staging round trips;
 // profiles/r12_realtime_block.txt).  Plain global -> register -> LDS staging, the loads of tile t + 1 in flight behind the MFMAs of
 // tile t; thread (row = tid & 63, chunk = tid >> 6) stages the 32 code bytes, the {δ, β} pair, the weight piece and the Vc entry of its
-// (row, chunk) — the chunk, hence the tap, is wave-uniform.  No K split over workgroups, no atomics, nothing exchanged between
-// workgroups.  The per-chunk body — the MFMA, then cvt + 2 fma per accumulator register (48 VALU per MFMA) behind 8 broadcast LDS
+// (row, chunk) — the chunk, hence the tap, is wave-uniform.  No atomics, nothing exchanged between workgroups; the long-K low-M layers run
+// K-split over workgroups in two launches (dgq_gemm_blockq_splitk: the same walk over 1/S of the K tiles, raw accumulators for the
+// family's combine, gemm_block.h / gemm_mx_split.hip — by a plan of this kernel's own there).  The per-chunk body — the MFMA, then cvt + 2 fma per accumulator register (48 VALU per MFMA) behind 8 broadcast LDS
 // reads of {δ, β} — is what a faster loop has to attack: several MFMA tiles per wave, the β·Vc term as an fp32 MFMA pass.
 #include "gemm_block.h"
 
@@ -36,8 +37,11 @@ constexpr int BQ_A = BLK_CH * BLK_BM * 32;                   // [chunk][row][32 
 constexpr int BQ_DB = BLK_CH * BLK_BM * 8, BQ_VC = BLK_CH * BLK_BN * 4;
 constexpr int bq_w_bytes(int wbits) { return BLK_CH * BLK_BN * (wbits == 4 ? 16 : 32); }
 
-template <int WBITS, typename TOut>
-__global__ __launch_bounds__(BLK_NT) void gemm_blockq_kernel(GemmParams p, BlockGather q, BlockqOperand o) {
+// One workgroup's walk: un-split (SPLIT false) the whole K and the store epilogue; split, K tiles [blockIdx.z·z.tps, + z.tps) and each
+// wave's raw accf into z.slab (gemm_block.h) — the gather, the staging, the LDS images and the chunk body are the same text.  A split may
+// begin inside a tap (the gather is per chunk), the padding chunks fall to the last split, and R[m] / zw belong to the combine.
+template <int WBITS, typename TOut, bool SPLIT>
+__device__ __forceinline__ void gemm_blockq_tile(const GemmParams& p, const BlockGather& q, const BlockqOperand& o, const BlockSplit& z) {
     constexpr int RING = block_ring(BQ_A + bq_w_bytes(WBITS) + BQ_DB + BQ_VC);
     __shared__ __attribute__((aligned(16))) uint8_t smem[RING + BLK_VEC];
     DGQ_DIAG_DECL
@@ -56,7 +60,7 @@ __global__ __launch_bounds__(BLK_NT) void gemm_blockq_kernel(GemmParams p, Block
     const float* vcrow = o.vc + (int64_t)n * q.nchp;
 
     // ---- epilogue vectors: R[m] (the in-image taps' rho in tap order), the column constants
-    if (r.tid < BLK_BM) block_vectors(vtab, vtab + 3 * BLK_BM, r.tid, p, n, block_rowsum_taps(q, row, p.rowsum), p.zw[n]);
+    if (!SPLIT && r.tid < BLK_BM) block_vectors(vtab, vtab + 3 * BLK_BM, r.tid, p, n, block_rowsum_taps(q, row, p.rowsum), p.zw[n]);
 
     // ---- staging registers of one K tile
     uint4 ra0, ra1, rw0, rw1;
@@ -100,11 +104,12 @@ __global__ __launch_bounds__(BLK_NT) void gemm_blockq_kernel(GemmParams p, Block
 #pragma unroll
     for (int i = 0; i < 16; ++i) accf[0][0][i] = 0.0f;
     const int nkt = (q.nch + BLK_CH - 1) / BLK_CH;
-    load_tile(0);
-    for (int kt = 0; kt < nkt; ++kt) {
+    const int kt0 = SPLIT ? (int)blockIdx.z * z.tps : 0, kt1 = SPLIT ? min(kt0 + z.tps, nkt) : nkt;
+    load_tile(kt0);
+    for (int kt = kt0; kt < kt1; ++kt) {
         store_tile();
         __syncthreads();
-        if (kt + 1 < nkt) load_tile(kt + 1);
+        if (kt + 1 < kt1) load_tile(kt + 1);
 #pragma unroll
         for (int ii = 0; ii < BLK_CH / 2; ++ii) {
             const int ci = 2 * ii + r.wave_k;               // this K wave's chunks of the tile
@@ -138,29 +143,66 @@ __global__ __launch_bounds__(BLK_NT) void gemm_blockq_kernel(GemmParams p, Block
         }
         __syncthreads();
     }
-    block_store<TOut, RING>(p, smem, r, nkt, accf DGQ_DIAG_ARG);
+    if constexpr (SPLIT) block_store_partial(z, r, accf[0][0]);
+    else block_store<TOut, RING>(p, smem, r, nkt, accf DGQ_DIAG_ARG);
     DGQ_DIAG_FLUSH(blockq, BLK_NW, r.wid, r.lane);
 }
 
+template <int WBITS, typename TOut>
+__global__ __launch_bounds__(BLK_NT) void gemm_blockq_kernel(GemmParams p, BlockGather q, BlockqOperand o) {
+    gemm_blockq_tile<WBITS, TOut, false>(p, q, o, BlockSplit{});
+}
 template <int WBITS>
-struct BlockqKernel { template <typename TOut> static constexpr auto fn = gemm_blockq_kernel<WBITS, TOut>; };
+__global__ __launch_bounds__(BLK_NT) void gemm_blockq_split_kernel(GemmParams p, BlockGather q, BlockqOperand o, BlockSplit z) {
+    gemm_blockq_tile<WBITS, float, true>(p, q, o, z);
+}
+
+template <int WBITS>
+struct BlockqKernel {
+    template <typename TOut> static constexpr auto fn = gemm_blockq_kernel<WBITS, TOut>;
+    static constexpr auto split = gemm_blockq_split_kernel<WBITS>;
+};
 
 }  // namespace
 
-extern "C" int dgq_gemm_blockq(const dgq_gemm_args_t* g, const dgq_gemm_block_t* blk, void* stream) {
-    const char* who = "dgq_gemm_blockq";
-    DGQ_CHECK_ARG(g && blk && blk->table && blk->vc, "dgq_gemm_blockq: null pointer");
+// what both entries do in front of their launch: the family's set-up and this format's operand
+static int gemm_blockq_setup(const char* who, const dgq_gemm_args_t* g, const dgq_gemm_block_t* blk, GemmParams& p, BlockGather& q, BlockqOperand& o) {
+    DGQ_CHECK_ARG(g && blk && blk->table && blk->vc, "%s: null pointer", who);
     const dgq_gemm_args_t& a = *g;
     const dgq_gemm_block_t& k = *blk;
-    DGQ_CHECK_ARG(a.w_bits == 4 || a.w_bits == 8, "dgq_gemm_blockq: w_bits=%d unsupported", a.w_bits);
-    DGQ_CHECK_ARG(a.rowsum_parts == 1, "dgq_gemm_blockq: rowsum is the quantiser's rho, one part");
-    GemmParams p;
-    BlockGather q;
+    DGQ_CHECK_ARG(a.w_bits == 4 || a.w_bits == 8, "%s: w_bits=%d unsupported", who, a.w_bits);
+    DGQ_CHECK_ARG(a.rowsum_parts == 1, "%s: rowsum is the quantiser's rho, one part", who);
     const int rc = block_gemm_setup(who, a, k.B, k.H, k.W, k.C, k.kh, k.kw, k.stride, k.pad, k.ups, true, p, q);
     if (rc != DGQ_OK) return rc;
-    DGQ_CHECK_ARG(k.ldt >= q.cpb, "dgq_gemm_blockq: table pitch %d < %d blocks", k.ldt, q.cpb);
-    DGQ_CHECK_ARG((reinterpret_cast<uintptr_t>(k.table) & 7) == 0, "dgq_gemm_blockq: the table must be 8-byte aligned");
-    const BlockqOperand o = {reinterpret_cast<const float2*>(k.table), k.ldt, k.vc};
+    DGQ_CHECK_ARG(k.ldt >= q.cpb, "%s: table pitch %d < %d blocks", who, k.ldt, q.cpb);
+    DGQ_CHECK_ARG((reinterpret_cast<uintptr_t>(k.table) & 7) == 0, "%s: the table must be 8-byte aligned", who);
+    o = {reinterpret_cast<const float2*>(k.table), k.ldt, k.vc};
+    return DGQ_OK;
+}
+
+extern "C" int dgq_gemm_blockq(const dgq_gemm_args_t* g, const dgq_gemm_block_t* blk, void* stream) {
+    const char* who = "dgq_gemm_blockq";
+    GemmParams p;
+    BlockGather q;
+    BlockqOperand o;
+    const int rc = gemm_blockq_setup(who, g, blk, p, q, o);
+    if (rc != DGQ_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    return a.w_bits == 4 ? block_gemm_launch<BlockqKernel<4>>(who, p, q, o, a.y_dtype, st) : block_gemm_launch<BlockqKernel<8>>(who, p, q, o, a.y_dtype, st);
+    return g->w_bits == 4 ? block_gemm_launch<BlockqKernel<4>>(who, p, q, o, g->y_dtype, st) : block_gemm_launch<BlockqKernel<8>>(who, p, q, o, g->y_dtype, st);
+}
+
+// The K split (gemm_block.h): splits = 0 asks this kernel's own plan (gemm_mx_split.hip: blockq_split_plan), which the family's launch
+// then clamps like a forced count; the combine runs with the zero-point term (R[m] over the in-image taps, zw[n]).
+extern "C" int dgq_gemm_blockq_splitk(const dgq_gemm_args_t* g, const dgq_gemm_block_t* blk, int splits, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "dgq_gemm_blockq_splitk";
+    GemmParams p;
+    BlockGather q;
+    BlockqOperand o;
+    const int rc = gemm_blockq_setup(who, g, blk, p, q, o);
+    if (rc != DGQ_OK) return rc;
+    DGQ_CHECK_ARG(splits >= 0, "%s: splits=%d", who, splits);
+    if (splits == 0) splits = blockq_split_plan(p.M, p.N, (q.nch + BLK_CH - 1) / BLK_CH, g->w_bits, workspace ? workspace_bytes : 0);
+    hipStream_t st = (hipStream_t)stream;
+    return g->w_bits == 4 ? block_gemm_launch_split<BlockqKernel<4>>(who, p, q, o, g->y_dtype, splits, workspace, workspace_bytes, st, true)
+                          : block_gemm_launch_split<BlockqKernel<8>>(who, p, q, o, g->y_dtype, splits, workspace, workspace_bytes, st, true);
 }

@@ -1033,14 +1033,16 @@ def dequant_act_block(codes, table, out):
     return out
 
 
-def gemm_blockq(q, geom, ab: "BlockActBinding", out_dtype, out=None, extra=None, ups=False):
+def gemm_blockq(q, geom, ab: "BlockActBinding", out_dtype, out=None, extra=None, ups=False, ksplit=1):
     """One dgq_gemm_blockq launch on q = quant_act_block(...) of the layer input; geom = (B, H, W, C, kh, kw, stride, pad) of the layer
-    (H, W: behind a folded upsample).  Returns y [M][N] (N/2 columns with the GEGLU epilogue)."""
+    (H, W: behind a folded upsample).  ksplit: 1 un-split; None the plan's K split (dgq_gemm_blockq_plan_splits), an int a forced one —
+    dgq_gemm_blockq_splitk, the split launch and its combine over workspace(device).  Returns y [M][N] (N/2 columns with the GEGLU
+    epilogue)."""
     _, table, rho = q
     k = _lib.GemmBlock()
     k.table, k.ldt, k.vc = table.data_ptr(), table.shape[1], ab.vc.data_ptr()
-    return _block_gemm_launch("dgq_gemm_blockq", k, q, geom, ab, out_dtype, out, extra, ups, w_bits=ab.pw.bits, rowsum=rho.data_ptr(),
-                              offset=ab.offset, zw=ab.pw.zw.data_ptr())
+    return _block_gemm_launch("dgq_gemm_blockq", k, q, geom, ab, out_dtype, out, extra, ups, ksplit=ksplit, w_bits=ab.pw.bits,
+                              rowsum=rho.data_ptr(), offset=ab.offset, zw=ab.pw.zw.data_ptr())
 
 
 def quant_act_mx6(x_cl: torch.Tensor, geom, pre=None, ln=None, ups=False, lds=None):
@@ -1147,17 +1149,23 @@ def _block_quant(ab, x_cl, geom, pre=None, ln=None, ups=False, pad_k=False):
 #: the K split of the MX layers (quant_linear, quant_conv2d, the batched Linear path): None = the library's plan per shape
 #: (dgq_gemm_mx_plan_splits), 1 = never, an int = forced — what _block_gemm hands to gemm_mx6 / gemm_mxint8 / gemm_mx4 / gemm_mxw8 as ``ksplit``
 MX_KSPLIT = None
+#: the K split of the int block layers (BlockActBinding; every layer the MX modes do not take runs as one): None = the library's plan per
+#: shape (dgq_gemm_blockq_plan_splits), 1 = never, an int = forced — what _block_gemm hands to gemm_blockq as ``ksplit``
+BLOCKQ_KSPLIT = None
 
 
 def _block_gemm(ab, q, geom, out_dtype, out=None, extra=None, ups=False):
-    if not ab.mx:
-        return gemm_blockq(q, geom, ab, out_dtype, out=out, extra=extra, ups=ups)
-    ksplit = MX_KSPLIT
+    ksplit = MX_KSPLIT if ab.mx else BLOCKQ_KSPLIT
     if ksplit is None:                                      # the plan says un-split: the un-split entry, and no workspace is asked for
         B, H, W, C, kh, kw, stride, pad = geom
         M = B * ((H + 2 * pad - kh) // stride + 1) * ((W + 2 * pad - kw) // stride + 1)
-        if _lib.load().dgq_gemm_mx_plan_splits(M, ab.pw.N, ab.Kp, WORKSPACE_BYTES) == 1:
+        lib = _lib.load()
+        plan = lib.dgq_gemm_mx_plan_splits(M, ab.pw.N, ab.Kp, WORKSPACE_BYTES) if ab.mx else \
+            lib.dgq_gemm_blockq_plan_splits(M, ab.pw.N, ab.Kp, ab.pw.bits, WORKSPACE_BYTES)
+        if plan == 1:
             ksplit = 1
+    if not ab.mx:
+        return gemm_blockq(q, geom, ab, out_dtype, out=out, extra=extra, ups=ups, ksplit=ksplit)
     gemm = gemm_mxw8 if ab.w_bits == 8 else {"mxfp6": gemm_mx6, "mxint8": gemm_mxint8, "mxfp4": gemm_mx4}[ab.fmt]
     return gemm(q, geom, ab, out_dtype, out=out, extra=extra, ups=ups, ksplit=ksplit)
 

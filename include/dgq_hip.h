@@ -55,8 +55,9 @@ extern "C" {
  *        dgq_gemm_mx_plan_splits, dgq_gemm_mx_workspace_bytes); W8 weights under both MX formats, dgq_pack_w_mx6x2 / dgq_gemm_mxw8 /
  *        dgq_gemm_mxw8_splitk with dgq_gemm_mxw8_t; the K split of the weight-only matrix-core layer (dgq_conv2d_wq_mfma16_splitk,
  *        dgq_conv2d_wq_mfma16_plan_splits, dgq_conv2d_wq_mfma16_workspace_bytes); the real-time MXFP4 mode, dgq_quant_act_mx4 /
- *        dgq_dequant_act_mx4 / dgq_gemm_mx4 / dgq_gemm_mx4_splitk with dgq_act_mx4_out_t and dgq_gemm_mx4_t — entries added only, the
- *        revision stays 123 */
+ *        dgq_dequant_act_mx4 / dgq_gemm_mx4 / dgq_gemm_mx4_splitk with dgq_act_mx4_out_t and dgq_gemm_mx4_t; the K split of the
+ *        real-time int block mode (dgq_gemm_blockq_splitk, dgq_gemm_blockq_plan_splits, dgq_gemm_blockq_workspace_bytes) — entries
+ *        added only, the revision stays 123 */
 #define DGQ_ABI_VERSION 123
 int dgq_version(void);
 const char* dgq_last_error(void);
@@ -443,8 +444,8 @@ typedef struct dgq_gemm_args {
 } dgq_gemm_args_t;
 int dgq_gemm_wxa8_batch(int n, const dgq_gemm_args_t* args, void* stream);
 
-/* dgq_gemm_blockq: the layer under the real-time block quantiser (dgq_quant_act_block), one launch, no K split, nothing exchanged
- * between workgroups.  With s the centred codes, qw' / zw the stored weight codes and their zero point, P[m,n,c] = Σ_{k∈c} s·qw' (a
+/* dgq_gemm_blockq: the layer under the real-time block quantiser (dgq_quant_act_block), one launch, nothing exchanged between
+ * workgroups (its K split: dgq_gemm_blockq_splitk below). With s the centred codes, qw' / zw the stored weight codes and their zero point, P[m,n,c] = Σ_{k∈c} s·qw' (a
  * FRESH int32 accumulator per 32-chunk c: no running total, no clear marks), Vc[n,c] = Σ_{k∈c} (qw' − zw):
  *   y[m,n] = gamma[n] + alpha[n]·( Σ_c ( δ[m,c]·float(P[m,n,c]) + β[m,c]·Vc[n,c] ) − zw[n]·R[m] ),   R[m] = Σ_c δ[m,c]·rs[m,c]
  * (chunks in ascending order, per chunk first the δ·P term, then the β·Vc term, one fp32 fma each).  Row m = (b·Ho + ho)·Wo + wo, chunk
@@ -461,6 +462,20 @@ typedef struct dgq_gemm_block {
     int B, H, W, C, kh, kw, stride, pad, ups;
 } dgq_gemm_block_t;
 int dgq_gemm_blockq(const dgq_gemm_args_t* g, const dgq_gemm_block_t* blk, void* stream);
+/* The K split of dgq_gemm_blockq for its long-K, low-M layers (the 3x3 convolutions of the 8x8 / 16x16 levels: 40 .. 160 tiles on 256
+ * CUs, each a serial walk of 45 .. 90 K tiles).  dgq_gemm_blockq_splitk: the same layer (same arguments, same checks, same epilogue
+ * forms) in two launches — S workgroups per 64x64 tile walk 1/S of the K tiles of 256 each (a split may begin inside a tap; the K
+ * padding falls to the last) and leave their raw fp32 accumulators in `workspace` (32 KiB per tile and split, 16-byte aligned), a combine
+ * kernel adds them and runs the un-split epilogue with R[m] and zw[n] formed as above.  The sum has one order — s ascending inside each
+ * of the tile's two K waves, then wave 0 + wave 1, the zero-point term applied once — so the result is deterministic and EQUALS
+ * dgq_gemm_blockq's wherever the fp32 additions are exact; elsewhere it differs by the rounding of the 2S − 1 additions of partials.
+ * No atomics, no counters; capture-safe.  splits: 0 = the plan's choice, >= 1 forced; either is clamped to the K tiles and to what the
+ * workspace holds, and no split is empty; one split, a NULL workspace or one too small for two splits give dgq_gemm_blockq itself.
+ * dgq_gemm_blockq_plan_splits: the S the plan takes for a shape, w_bits and a workspace of that size (1: un-split) — constants of this
+ * kernel's own (its K tile costs more than an MX one); dgq_gemm_blockq_workspace_bytes: what that plan needs without a limit (0: un-split). */
+int dgq_gemm_blockq_splitk(const dgq_gemm_args_t* g, const dgq_gemm_block_t* blk, int splits, void* workspace, size_t workspace_bytes, void* stream);
+int dgq_gemm_blockq_plan_splits(int M, int N, int Kp, int w_bits, size_t workspace_bytes);
+size_t dgq_gemm_blockq_workspace_bytes(int M, int N, int Kp, int w_bits);
 
 /* ---- real-time MXFP6 activations on the block-scaled matrix cores (W4A6; a mode of this library) -------------------------------------
  * Every block of DGQ_KCHUNK = 32 consecutive channels of every input row gets ONE power-of-two scale 2^E and 32 FP6 E2M3 codes (sign, 2
