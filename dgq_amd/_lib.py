@@ -50,6 +50,7 @@ SIGNATURES = {
     "dgq_attention_sync_timeouts": [],
     "dgq_minmax_rows_cols": [_vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp],
     "dgq_linear_smallm_batch": [_vp, _i, _i, _i, _i64, _i, _i, _vp, _i, _vp],
+    "dgq_linear_smallm_mx_batch": [_vp, _i, _i, _i, _i64, _i, _i, _i, _vp, _i, _vp],
     "dgq_quant_act_batch": [_i, _vp, _vp],
     "dgq_quant_act_variant": [_vp],
     "dgq_act_row_params": [_vp, _i, _vp, ctypes.c_size_t, _vp, _vp, _vp],
@@ -115,6 +116,11 @@ class SmallMProblem(ctypes.Structure):
     """dgq_smallm_problem_t of include/dgq_hip.h"""
     _fields_ = [("wpacked", _vp), ("alpha", _vp), ("zw", _vp), ("gamma", _vp), ("vn", _vp), ("mdelta", _vp), ("mzp", _vp),
                 ("y", _vp), ("ldy", _i), ("N", _i), ("Kp", _i), ("w_bits", _i), ("a_bits", _i)]
+
+
+class SmallMMxProblem(ctypes.Structure):
+    """dgq_smallm_mx_problem_t of include/dgq_hip.h"""
+    _fields_ = [("wpacked", _vp), ("alpha", _vp), ("gamma", _vp), ("y", _vp), ("ldy", _i), ("N", _i), ("Kp", _i)]
 
 
 class QuantActArgs(ctypes.Structure):

@@ -77,6 +77,113 @@ __device__ __forceinline__ void dgq_affine_code4_fast(const float (&x)[4], float
 }
 
 
+// ---- The MX block statements (dgq_amd/quant/quant_layer.py mx6_block / mxint8_block / mx4_block), shared by the stand-alone
+// quantisers (quant_mx6.hip, quant_mxint8.hip, quant_mx4.hip) and the batch-row Linear kernel that quantises its own input
+// (linear_smallm_mx.hip) — one implementation, so that both produce the same codes and scale bytes.  A lane holds four consecutive
+// x′ of a 32-channel block and the block's eight lanes are consecutive lanes of the wave, all of them running.
+
+// max |x′| of the lane's block as an integer (the bits of a non-negative finite float order like the value): a 3-step in-wave max
+__device__ __forceinline__ uint32_t mx_block_amax_bits(const float (&v)[4]) {
+    uint32_t am = max(max(__float_as_uint(v[0]) & 0x7FFFFFFFu, __float_as_uint(v[1]) & 0x7FFFFFFFu),
+                      max(__float_as_uint(v[2]) & 0x7FFFFFFFu, __float_as_uint(v[3]) & 0x7FFFFFFFu));
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o, 64));
+    return am;
+}
+
+// 2^e for e in [−127, 127] (−127: the subnormal 2^−127)
+__device__ __forceinline__ float mx6_pow2(int e) {
+    return e >= -126 ? __uint_as_float((uint32_t)(e + 127) << 23) : __uint_as_float(0x00400000u);
+}
+
+// E2M3 code of v (|v| < 8, finite): sign | magnitude, round to nearest even on the grid, saturating at 7.5; magnitude 0 -> +0
+__device__ __forceinline__ uint32_t mx6_code(float v) {
+    const float a = fabsf(v);
+    const float inv_step = a < 2.0f ? 8.0f : (a < 4.0f ? 4.0f : 2.0f);
+    const float step = a < 2.0f ? 0.125f : (a < 4.0f ? 0.25f : 0.5f);
+    const float q = fminf(rintf(a * inv_step) * step, 7.5f);                     // on the grid (a step boundary rounds onto the next range's first value)
+    const uint32_t qb = __float_as_uint(q);
+    const uint32_t mag = q < 1.0f ? (uint32_t)(q * 8.0f) : ((((qb >> 23) - 126u) << 3) | ((qb >> 20) & 7u));
+    return mag ? (mag | ((__float_as_uint(v) >> 26) & 0x20u)) : 0u;
+}
+
+// MXFP6: the block's E (scale byte E + 127) and the lane's four codes, element j at bits 6j .. 6j + 5
+__device__ __forceinline__ uint32_t mx6_block_codes(const float (&v)[4], int& E) {
+    const uint32_t am = mx_block_amax_bits(v);
+    E = max((int)(am >> 23) - 129, -127);                  // floor(log2 amax) − 2; subnormal or zero amax: −127
+    const float inv = mx6_pow2(-E);
+    return mx6_code(v[0] * inv) | (mx6_code(v[1] * inv) << 6) | (mx6_code(v[2] * inv) << 12) | (mx6_code(v[3] * inv) << 18);
+}
+
+// 2^e for e in [−126, 127]
+__device__ __forceinline__ float mxint8_pow2(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
+
+// E2M3 magnitude code of n/2 for an integer n in [0, 15]: 0.5 is the subnormal 4/8; n >= 2 is (1 + m/8)·2^(p−1) with p = floor(log2 n)
+__device__ __forceinline__ uint32_t mxint8_half_code(uint32_t n) {
+    const uint32_t p = 31u - (uint32_t)__clz((int)(n | 1u));
+    return n < 2u ? n << 2 : ((p << 3) | ((n << (3u - p)) & 7u));
+}
+
+// the two plane codes of s in [−127, 127]: hi = sign-magnitude h/2 (h = s >> 4; h = 0 is +0), lo = l/2 (l = s & 15)
+__device__ __forceinline__ void mxint8_split(int s, uint32_t& hi, uint32_t& lo) {
+    const int h = s >> 4;
+    hi = mxint8_half_code((uint32_t)(h < 0 ? -h : h)) | (h < 0 ? 0x20u : 0u);
+    lo = mxint8_half_code((uint32_t)(s & 15));
+}
+
+// MXINT8: the block's E and the lane's four codes as their two 6-bit planes, element j at bits 6j .. 6j + 5 of each
+__device__ __forceinline__ void mxint8_block_codes(const float (&v)[4], int& E, uint32_t& hi, uint32_t& lo) {
+    const uint32_t am = mx_block_amax_bits(v);
+    E = max((int)(am >> 23) - 127, -120);                  // floor(log2 amax); zero, subnormal or tiny amax: −120 (finite amax: <= 127)
+    const float inv = mxint8_pow2(6 - E);
+    hi = 0u; lo = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int sj = (int)fminf(fmaxf(rintf(v[j] * inv), -127.0f), 127.0f);
+        uint32_t h6, l6;
+        mxint8_split(sj, h6, l6);
+        hi |= h6 << (6 * j); lo |= l6 << (6 * j);
+    }
+}
+
+// 2^e for e in [−127, 127] (−127: the subnormal 2^−127)
+__device__ __forceinline__ float mx4_pow2(int e) {
+    return e >= -126 ? __uint_as_float((uint32_t)(e + 127) << 23) : __uint_as_float(0x00400000u);
+}
+
+// E2M1 code of v (|v| < 8, finite): sign << 3 | exponent << 1 | mantissa, round to nearest, ties to the even code, saturating at 6;
+// magnitude 0 -> +0
+__device__ __forceinline__ uint32_t mx4_code(float v) {
+    const float a = fabsf(v);
+    const float inv_step = a < 2.0f ? 2.0f : (a < 4.0f ? 1.0f : 0.5f);
+    const float step = a < 2.0f ? 0.5f : (a < 4.0f ? 1.0f : 2.0f);
+    const float q = fminf(rintf(a * inv_step) * step, 6.0f);                     // on the grid (a step boundary rounds onto the next range's first value)
+    const uint32_t qb = __float_as_uint(q);
+    const uint32_t mag = q < 1.0f ? (uint32_t)(q * 2.0f) : ((((qb >> 23) - 126u) << 1) | ((qb >> 22) & 1u));
+    return mag ? (mag | ((__float_as_uint(v) >> 28) & 0x8u)) : 0u;
+}
+
+// MXFP4: the block's E and the block's 128 bits (element j at bits 4j .. 4j + 3) in the block's FIRST lane: a lane's four codes are 16
+// bits, a lane pair makes a word, the first lane collects the four (the other lanes' return values are not the block)
+__device__ __forceinline__ uint4 mx4_block_codes(const float (&v)[4], int& E) {
+    const uint32_t am = mx_block_amax_bits(v);
+    E = max((int)(am >> 23) - 129, -127);                  // floor(log2 amax) − 2; subnormal or zero amax: −127
+    const float inv = mx4_pow2(-E);
+    const uint32_t piece = mx4_code(v[0] * inv) | (mx4_code(v[1] * inv) << 4) | (mx4_code(v[2] * inv) << 8) | (mx4_code(v[3] * inv) << 12);
+    const uint32_t w = piece | ((uint32_t)__shfl_down((int)piece, 1, 64) << 16);
+    uint4 blk;
+    blk.x = w;
+    blk.y = (uint32_t)__shfl_down((int)w, 2, 64);
+    blk.z = (uint32_t)__shfl_down((int)w, 4, 64);
+    blk.w = (uint32_t)__shfl_down((int)w, 6, 64);
+    return blk;
+}
+
+// a lane's word of the 192-bit string of a 6-bit plane: lanes 4g .. 4g + 3 hold 96 bits = 3 words; lane t = lane & 3 < 3 writes word t
+// at byte 3·(lane of the block) + t of the block from its own 24 bits and the next lane's (`next`: __shfl_down of `piece` by 1)
+__device__ __forceinline__ uint32_t mx6_lane_word(uint32_t piece, uint32_t next, int t) { return (piece >> (8 * t)) | (next << (24 - 8 * t)); }
+
+
 // ---- Block-staged convolution quantisers (quant_act_conv_kernel, gemm_convq_kernel): a workgroup stages the input patch of its tile of
 // output positions in LDS and every row of the tile gathers its codes from it through the kpat table.  What the gather needs of the
 // tables depends on the column kp alone, so it is resolved ONCE per workgroup, where the tables are staged, and not per code:

@@ -23,22 +23,7 @@ struct Mx4QuantProblem {
     uint8_t* codes; uint8_t* scale; int lds;
 };
 
-// 2^e for e in [−127, 127] (−127: the subnormal 2^−127)
-__device__ __forceinline__ float mx4_pow2(int e) {
-    return e >= -126 ? __uint_as_float((uint32_t)(e + 127) << 23) : __uint_as_float(0x00400000u);
-}
-
-// E2M1 code of v (|v| < 8, finite): sign << 3 | exponent << 1 | mantissa, round to nearest, ties to the even code, saturating at 6;
-// magnitude 0 -> +0
-__device__ __forceinline__ uint32_t mx4_code(float v) {
-    const float a = fabsf(v);
-    const float inv_step = a < 2.0f ? 2.0f : (a < 4.0f ? 1.0f : 0.5f);
-    const float step = a < 2.0f ? 0.5f : (a < 4.0f ? 1.0f : 2.0f);
-    const float q = fminf(rintf(a * inv_step) * step, 6.0f);                     // on the grid (a step boundary rounds onto the next range's first value)
-    const uint32_t qb = __float_as_uint(q);
-    const uint32_t mag = q < 1.0f ? (uint32_t)(q * 2.0f) : ((((qb >> 23) - 126u) << 1) | ((qb >> 22) & 1u));
-    return mag ? (mag | ((__float_as_uint(v) >> 28) & 0x8u)) : 0u;
-}
+// (mx4_pow2, mx4_code and the block statement mx4_block_codes: quant_common.h — shared with linear_smallm_mx.hip)
 
 template <typename TIn>
 __global__ __launch_bounds__(256) void quant_mx4_kernel(Mx4QuantProblem p) {
@@ -50,21 +35,8 @@ __global__ __launch_bounds__(256) void quant_mx4_kernel(Mx4QuantProblem p) {
     uint8_t* crow = p.codes + (int64_t)row * (in.C / 2);
     uint8_t* srow = p.scale + (int64_t)row * p.lds;
     quant_block_walk<TIn>(in, s, lane, [&](const float (&v)[4], int c, bool inside, int) {
-        // max |x′| as an integer (the bits of a non-negative finite float order like the value)
-        uint32_t am = max(max(__float_as_uint(v[0]) & 0x7FFFFFFFu, __float_as_uint(v[1]) & 0x7FFFFFFFu),
-                          max(__float_as_uint(v[2]) & 0x7FFFFFFFu, __float_as_uint(v[3]) & 0x7FFFFFFFu));
-#pragma unroll
-        for (int o = 1; o < 8; o <<= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o, 64));
-        const int E = max((int)(am >> 23) - 129, -127);    // floor(log2 amax) − 2; subnormal or zero amax: −127
-        const float inv = mx4_pow2(-E);
-        const uint32_t piece = mx4_code(v[0] * inv) | (mx4_code(v[1] * inv) << 4) | (mx4_code(v[2] * inv) << 8) | (mx4_code(v[3] * inv) << 12);
-        // lanes 8g .. 8g + 7 hold the block's 128 bits, 16 each: a lane pair makes a word, the first lane of the block collects the four
-        const uint32_t w = piece | ((uint32_t)__shfl_down((int)piece, 1, 64) << 16);
-        uint4 blk;
-        blk.x = w;
-        blk.y = (uint32_t)__shfl_down((int)w, 2, 64);
-        blk.z = (uint32_t)__shfl_down((int)w, 4, 64);
-        blk.w = (uint32_t)__shfl_down((int)w, 6, 64);
+        int E;
+        const uint4 blk = mx4_block_codes(v, E);           // the block's 128 bits in its first lane
         if (inside && (lane & 7) == 0) {
             *reinterpret_cast<uint4*>(crow + (c >> 5) * 16) = blk;
             srow[c >> 5] = (uint8_t)(E + 127);

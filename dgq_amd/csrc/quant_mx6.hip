@@ -21,21 +21,7 @@ struct Mx6QuantProblem {
     uint8_t* codes; uint8_t* scale; int lds;
 };
 
-// 2^e for e in [−127, 127] (−127: the subnormal 2^−127)
-__device__ __forceinline__ float mx6_pow2(int e) {
-    return e >= -126 ? __uint_as_float((uint32_t)(e + 127) << 23) : __uint_as_float(0x00400000u);
-}
-
-// E2M3 code of v (|v| < 8, finite): sign | magnitude, round to nearest even on the grid, saturating at 7.5; magnitude 0 -> +0
-__device__ __forceinline__ uint32_t mx6_code(float v) {
-    const float a = fabsf(v);
-    const float inv_step = a < 2.0f ? 8.0f : (a < 4.0f ? 4.0f : 2.0f);
-    const float step = a < 2.0f ? 0.125f : (a < 4.0f ? 0.25f : 0.5f);
-    const float q = fminf(rintf(a * inv_step) * step, 7.5f);                     // on the grid (a step boundary rounds onto the next range's first value)
-    const uint32_t qb = __float_as_uint(q);
-    const uint32_t mag = q < 1.0f ? (uint32_t)(q * 8.0f) : ((((qb >> 23) - 126u) << 3) | ((qb >> 20) & 7u));
-    return mag ? (mag | ((__float_as_uint(v) >> 26) & 0x20u)) : 0u;
-}
+// (mx6_pow2, mx6_code and the block statement mx6_block_codes: quant_common.h — shared with linear_smallm_mx.hip)
 
 template <typename TIn>
 __global__ __launch_bounds__(256) void quant_mx6_kernel(Mx6QuantProblem p) {
@@ -47,18 +33,12 @@ __global__ __launch_bounds__(256) void quant_mx6_kernel(Mx6QuantProblem p) {
     uint8_t* crow = p.codes + (int64_t)row * (in.C / 4 * 3);
     uint8_t* srow = p.scale + (int64_t)row * p.lds;
     quant_block_walk<TIn>(in, s, lane, [&](const float (&v)[4], int c, bool inside, int) {
-        // max |x′| as an integer (the bits of a non-negative finite float order like the value)
-        uint32_t am = max(max(__float_as_uint(v[0]) & 0x7FFFFFFFu, __float_as_uint(v[1]) & 0x7FFFFFFFu),
-                          max(__float_as_uint(v[2]) & 0x7FFFFFFFu, __float_as_uint(v[3]) & 0x7FFFFFFFu));
-#pragma unroll
-        for (int o = 1; o < 8; o <<= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o, 64));
-        const int E = max((int)(am >> 23) - 129, -127);    // floor(log2 amax) − 2; subnormal or zero amax: −127
-        const float inv = mx6_pow2(-E);
-        const uint32_t piece = mx6_code(v[0] * inv) | (mx6_code(v[1] * inv) << 6) | (mx6_code(v[2] * inv) << 12) | (mx6_code(v[3] * inv) << 18);
+        int E;
+        const uint32_t piece = mx6_block_codes(v, E);
         const uint32_t next = (uint32_t)__shfl_down((int)piece, 1, 64);
         const int t = lane & 3;                            // lanes 4g .. 4g + 3 hold 96 bits = 3 words; lane t < 3 writes word t
         if (inside) {
-            if (t < 3) *reinterpret_cast<uint32_t*>(crow + (c >> 2) * 3 + t) = (piece >> (8 * t)) | (next << (24 - 8 * t));
+            if (t < 3) *reinterpret_cast<uint32_t*>(crow + (c >> 2) * 3 + t) = mx6_lane_word(piece, next, t);
             if ((lane & 7) == 0) srow[c >> 5] = (uint8_t)(E + 127);
         }
     });

@@ -24,21 +24,7 @@ struct MxInt8QuantProblem {
     uint8_t* codes; uint8_t* scale; int lds;
 };
 
-// 2^e for e in [−126, 127]
-__device__ __forceinline__ float mxint8_pow2(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
-
-// E2M3 magnitude code of n/2 for an integer n in [0, 15]: 0.5 is the subnormal 4/8; n >= 2 is (1 + m/8)·2^(p−1) with p = floor(log2 n)
-__device__ __forceinline__ uint32_t mxint8_half_code(uint32_t n) {
-    const uint32_t p = 31u - (uint32_t)__clz((int)(n | 1u));
-    return n < 2u ? n << 2 : ((p << 3) | ((n << (3u - p)) & 7u));
-}
-
-// the two plane codes of s in [−127, 127]: hi = sign-magnitude h/2 (h = s >> 4; h = 0 is +0), lo = l/2 (l = s & 15)
-__device__ __forceinline__ void mxint8_split(int s, uint32_t& hi, uint32_t& lo) {
-    const int h = s >> 4;
-    hi = mxint8_half_code((uint32_t)(h < 0 ? -h : h)) | (h < 0 ? 0x20u : 0u);
-    lo = mxint8_half_code((uint32_t)(s & 15));
-}
+// (mxint8_pow2, mxint8_split and the block statement mxint8_block_codes: quant_common.h — shared with linear_smallm_mx.hip)
 
 template <typename TIn>
 __global__ __launch_bounds__(256) void quant_mxint8_kernel(MxInt8QuantProblem p) {
@@ -50,29 +36,17 @@ __global__ __launch_bounds__(256) void quant_mxint8_kernel(MxInt8QuantProblem p)
     uint8_t* crow = p.codes + (int64_t)row * (in.C / 32 * 48);
     uint8_t* srow = p.scale + (int64_t)row * p.lds;
     quant_block_walk<TIn>(in, s, lane, [&](const float (&v)[4], int c, bool inside, int) {
-        // max |x′| as an integer (the bits of a non-negative finite float order like the value)
-        uint32_t am = max(max(__float_as_uint(v[0]) & 0x7FFFFFFFu, __float_as_uint(v[1]) & 0x7FFFFFFFu),
-                          max(__float_as_uint(v[2]) & 0x7FFFFFFFu, __float_as_uint(v[3]) & 0x7FFFFFFFu));
-#pragma unroll
-        for (int o = 1; o < 8; o <<= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o, 64));
-        const int E = max((int)(am >> 23) - 127, -120);    // floor(log2 amax); zero, subnormal or tiny amax: −120 (finite amax: <= 127)
-        const float inv = mxint8_pow2(6 - E);
-        uint32_t hi = 0u, lo = 0u;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int sj = (int)fminf(fmaxf(rintf(v[j] * inv), -127.0f), 127.0f);
-            uint32_t h6, l6;
-            mxint8_split(sj, h6, l6);
-            hi |= h6 << (6 * j); lo |= l6 << (6 * j);
-        }
+        int E;
+        uint32_t hi, lo;
+        mxint8_block_codes(v, E, hi, lo);
         const uint32_t hi_next = (uint32_t)__shfl_down((int)hi, 1, 64);
         const uint32_t lo_next = (uint32_t)__shfl_down((int)lo, 1, 64);
         const int t = lane & 3;                            // lanes 4g .. 4g + 3 hold 96 bits = 3 words per plane; lane t < 3 writes word t
         if (inside) {
             if (t < 3) {
                 uint8_t* blk = crow + (c >> 5) * 48 + ((c >> 2) & 7) * 3 + t;      // (12·(lane group of the block) + 4t: 4-byte aligned)
-                *reinterpret_cast<uint32_t*>(blk) = (hi >> (8 * t)) | (hi_next << (24 - 8 * t));
-                *reinterpret_cast<uint32_t*>(blk + 24) = (lo >> (8 * t)) | (lo_next << (24 - 8 * t));
+                *reinterpret_cast<uint32_t*>(blk) = mx6_lane_word(hi, hi_next, t);
+                *reinterpret_cast<uint32_t*>(blk + 24) = mx6_lane_word(lo, lo_next, t);
             }
             if ((lane & 7) == 0) srow[c >> 5] = (uint8_t)(E + 127);
         }

@@ -1664,6 +1664,55 @@ def linear_smallm_batch(x2d: torch.Tensor, bindings, pre_act=0):
     return outs
 
 
+#: the batch-row Linear layers of the real-time MX modes (MxActBinding, W4) in one launch (linear_smallm_mx_batch) instead of a quantiser
+#: and a GEMM launch per layer: the time_emb_proj group of a forward (TembGroup.get).
+#: Off: not measured faster on an SD step yet (profiles/r28_mx_smallm_batch.txt).
+MX_SMALLM_BATCH = False
+
+
+def mx_smallm_ok(ab, x2d):
+    """True when linear_smallm_mx_batch takes a Linear layer under binding ab on the input x2d [M][K]"""
+    M, K = x2d.shape
+    return (ab.mx and ab.w_bits == 4 and ab.pw.taps == 1 and ab.pw.K == K and 1 <= M <= SMALLM_MAX_M and K % 32 == 0 and K <= SMALLM_MAX_K
+            and x2d.dtype in _lib.DTYPE_CODE and x2d.stride(1) == 1 and x2d.stride(0) % 4 == 0 and x2d.data_ptr() % 16 == 0)
+
+
+def linear_smallm_mx_batch(x2d: torch.Tensor, bindings, pre_act=0):
+    """[ab.pw(mx_quantiser(act(x2d))) for ab in bindings] for W4 Linear layers under ONE real-time MX format (MxActBinding) sharing the
+    input x2d [M <= 16][K] in ONE launch per 24 layers (dgq_linear_smallm_mx_batch): each workgroup quantises x2d itself, with the block
+    statement of quant_act_mx6 / _mxint8 / _mx4, and streams its columns of the layer's MX weight image.  pre_act 1: SiLU(x2d)."""
+    who = "linear_smallm_mx_batch"
+    assert x2d.dim() == 2 and x2d.stride(1) == 1 and x2d.dtype in _lib.DTYPE_CODE, who + ": x2d [M][K], unit channel stride"
+    M, K = x2d.shape
+    assert 1 <= M <= SMALLM_MAX_M, "%s: M=%d (1 .. %d)" % (who, M, SMALLM_MAX_M)
+    assert K % 32 == 0 and K <= SMALLM_MAX_K, "%s: K=%d must be a multiple of 32, <= %d" % (who, K, SMALLM_MAX_K)
+    assert all(getattr(ab, "mx", False) and ab.w_bits == 4 for ab in bindings), who + ": every binding must be a W4 MxActBinding"
+    assert len({ab.fmt for ab in bindings}) == 1, who + ": the bindings must share one MX format"
+    fmt = MX_FORMAT_BITS[bindings[0].fmt]
+    code = _lib.DTYPE_CODE[x2d.dtype]
+    outs = []
+    for i0 in range(0, len(bindings), SMALLM_MAX_PROBLEMS):
+        chunk = bindings[i0:i0 + SMALLM_MAX_PROBLEMS]
+        probs = (_lib.SmallMMxProblem * len(chunk))()
+        keep = []
+        for q, ab in zip(probs, chunk):
+            pw = ab.pw
+            assert pw.K == K and pw.taps == 1, who + ": a Linear layer of K input channels"
+            y = torch.empty((M, pw.N), dtype=x2d.dtype, device=x2d.device)
+            q.wpacked, q.alpha, q.gamma = ab.wpacked.data_ptr(), pw.alpha.data_ptr(), ab.gamma.data_ptr()
+            q.y, q.ldy, q.N, q.Kp = y.data_ptr(), y.stride(0), pw.N, ab.Kp
+            keep.append(y)
+
+        def issue(_keep=(x2d, chunk, keep), probs=probs, n=len(chunk)):
+            _lib_call("dgq_linear_smallm_mx_batch", _lib.ptr(x2d), code, M, K, x2d.stride(0), pre_act, fmt, n, _c.cast(probs, _c.c_void_p),
+                      code, _lib.stream())
+        issue()
+        if BLOCK_LAUNCH_HOOK is not None:
+            BLOCK_LAUNCH_HOOK(issue, "smallm", (M, sum(ab.pw.N for ab in chunk), K))
+        outs += keep
+    return outs
+
+
 def minmax_rows_cols(x2d: torch.Tensor, rows=True, cols=True):
     """Row-wise and column-wise (min, max) of a contiguous [R][C] view — the statistics of DGQ's calibration producer
     (dgq_minmax_rows_cols).  Returns (rowmin, rowmax, colmin, colmax), fp32, None for a pair that was not requested."""

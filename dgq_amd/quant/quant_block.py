@@ -69,8 +69,8 @@ class BaseQuantBlock(nn.Module):
 
 class TembGroup:
     """The time_emb_proj layers of one QuantModel.  The first resnet block that asks for its projection of a given
-    ``temb`` tensor triggers ONE batched launch (ops.linear_smallm_batch) for every layer of the group; the others pick
-    their result up.  Keyed by tensor identity, so it holds within one forward (and one graph capture) only."""
+    ``temb`` tensor triggers ONE batched launch (ops.linear_smallm_batch; with ops.MX_SMALLM_BATCH under a real-time MX format,
+    ops.linear_smallm_mx_batch) for every layer of the group; the others pick their result up.  Keyed by tensor identity, so it holds within one forward (and one graph capture) only."""
 
     def __init__(self, layers, epoch):
         self.layers = list(layers)
@@ -86,9 +86,15 @@ class TembGroup:
     def get(self, layer, temb):
         if self._src is not temb or self._seen != self.epoch[0]:
             binds = [l._binding() for l in self.layers]
-            if any(b.mode == "perK" or b.L != 1 for b in binds):
-                return None                                   # a grouped table on a 2-D input does not occur; be safe
-            self._out = dict(zip((id(l) for l in self.layers), ops.linear_smallm_batch(temb, binds, pre_act=1)))
+            if ops.MX_SMALLM_BATCH and all(ops.mx_smallm_ok(b, temb) for b in binds) and len({b.fmt for b in binds}) == 1:
+                outs = ops.linear_smallm_mx_batch(temb, binds, pre_act=1)     # every layer a W4 binding of one MX format: one launch
+            elif any(b.mode == "perK" or b.L != 1 for b in binds):
+                # a grouped table on a 2-D input does not occur; be safe.  A real-time binding (L = 0: rows, int blocks, a W8 MX layer or
+                # a mixed group) is not dgq_linear_smallm_batch's either: each layer runs on its own
+                return None
+            else:
+                outs = ops.linear_smallm_batch(temb, binds, pre_act=1)
+            self._out = dict(zip((id(l) for l in self.layers), outs))
             self._src, self._seen = temb, self.epoch[0]
         return self._out[id(layer)]
 

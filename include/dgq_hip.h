@@ -56,7 +56,8 @@ extern "C" {
  *        dgq_gemm_mxw8_splitk with dgq_gemm_mxw8_t; the K split of the weight-only matrix-core layer (dgq_conv2d_wq_mfma16_splitk,
  *        dgq_conv2d_wq_mfma16_plan_splits, dgq_conv2d_wq_mfma16_workspace_bytes); the real-time MXFP4 mode, dgq_quant_act_mx4 /
  *        dgq_dequant_act_mx4 / dgq_gemm_mx4 / dgq_gemm_mx4_splitk with dgq_act_mx4_out_t and dgq_gemm_mx4_t; the K split of the
- *        real-time int block mode (dgq_gemm_blockq_splitk, dgq_gemm_blockq_plan_splits, dgq_gemm_blockq_workspace_bytes) — entries
+ *        real-time int block mode (dgq_gemm_blockq_splitk, dgq_gemm_blockq_plan_splits, dgq_gemm_blockq_workspace_bytes); the batch-row
+ *        Linear layers of the MX modes in one launch (dgq_linear_smallm_mx_batch with dgq_smallm_mx_problem_t) — entries
  *        added only, the revision stays 123 */
 #define DGQ_ABI_VERSION 123
 int dgq_version(void);
@@ -710,6 +711,23 @@ typedef struct dgq_smallm_problem {
 } dgq_smallm_problem_t;
 int dgq_linear_smallm_batch(const void* x, int x_dtype, int M, int K, int64_t ldx, int pre_act, int n_problems,
                             const dgq_smallm_problem_t* probs, int y_dtype, void* stream);
+/* dgq_linear_smallm_mx_batch: the same batch under the real-time MX activation modes — y_l = gamma_l + alpha_l·Σ x̂·(q − z)_l for up to
+ * 24 W4 Linear layers that share one input x [M][K] (1 <= M <= 16, K % 32 == 0, K <= 2048; 16-byte aligned, ldx % 4 == 0) in ONE launch,
+ * x̂ = the block statement of dgq_quant_act_mx6 (a_format 6), dgq_quant_act_mxint8 (8) or dgq_quant_act_mx4 (4) on act(x) (pre_act 1:
+ * SiLU in fp32, as those quantisers' prologue), formed by each workgroup in LDS — the same codes and scale bytes, never written to
+ * memory.  wpacked = the layer's image of dgq_pack_w_mx6 [N][Kp/32][24], unchanged (16-byte aligned; Kp % DGQ_KTILE == 0, K <= Kp <=
+ * 2048), alpha = δw, gamma = bias.  Per 128-deep K step one block-scaled 16x16x128 MFMA (MXINT8: lo plane, then hi plane) into ONE
+ * fp32 accumulator per output over the whole K in ascending order: no K split, no atomics, deterministic.  The store is the plain
+ * epilogue of dgq_gemm_mx6 (no extras), one rounding into y_dtype (= x_dtype).  probs: host array, copied into the kernel arguments. */
+typedef struct dgq_smallm_mx_problem {
+    const void* wpacked;
+    const float* alpha;
+    const float* gamma;
+    void* y;
+    int ldy, N, Kp;
+} dgq_smallm_mx_problem_t;
+int dgq_linear_smallm_mx_batch(const void* x, int x_dtype, int M, int K, int64_t ldx, int pre_act, int a_format, int n_problems,
+                               const dgq_smallm_mx_problem_t* probs, int y_dtype, void* stream);
 
 /* ---- calibration producer --------------------------------------------------------
  * dgq_minmax_rows_cols: the statistics UniformAffineQuantizer.record_min_max_ema collects for DGQ's grouping
