@@ -51,6 +51,8 @@ SIGNATURES = {
     "dgq_minmax_rows_cols": [_vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp],
     "dgq_linear_smallm_batch": [_vp, _i, _i, _i, _i64, _i, _i, _vp, _i, _vp],
     "dgq_linear_smallm_mx_batch": [_vp, _i, _i, _i, _i64, _i, _i, _i, _vp, _i, _vp],
+    "dgq_gemm_mx_rows": [_vp, _i, _i, _vp, _i, _vp],
+    "dgq_gemm_mx_rows_plan": [_i, _i, _i, _i],
     "dgq_quant_act_batch": [_i, _vp, _vp],
     "dgq_quant_act_variant": [_vp],
     "dgq_act_row_params": [_vp, _i, _vp, ctypes.c_size_t, _vp, _vp, _vp],

@@ -953,7 +953,8 @@ def gemm_wxa8(codes, rowsum, M, ab: ActBinding, out_dtype, out: Optional[torch.T
 
 
 #: BLOCK_LAUNCH_HOOK(issue, kind, info): every launch of the real-time block mode — kind "quant" (dgq_quant_act_block; info = rows, C)
-#: or "gemm" (dgq_gemm_blockq; info = M, N, K).  A measurement hook (tools/profile_realtime_act.py), None in production.
+#: or "gemm" (dgq_gemm_blockq; info = M, N, K), "smallm" (linear_smallm_mx_batch) or "rows" (gemm_mx_rows; info = M, the columns of all
+#: problems, K).  A measurement hook (tools/profile_realtime_act.py), None in production.
 BLOCK_LAUNCH_HOOK = None
 
 
@@ -1170,6 +1171,64 @@ def _block_gemm(ab, q, geom, out_dtype, out=None, extra=None, ups=False):
     return gemm(q, geom, ab, out_dtype, out=out, extra=extra, ups=ups, ksplit=ksplit)
 
 
+#: the general-M Linear layers of the real-time MX modes (W4 MxActBinding) in one launch (gemm_mx_rows: the workgroup quantises its own
+#: rows in LDS) instead of a quantiser and a GEMM launch: what quant_linear and quant_linear_multi do with an eligible binding
+#: (mx_rows_ok).  Same bits either way.  Off: see DESIGN.md §8 and profiles/r29_mx_rows_fused.txt.
+MX_ROWS_FUSED = False
+MX_ROWS_MAX_PROBLEMS = 4
+
+
+def mx_rows_ok(ab, x2d, pre_act=0, n_sum=None):
+    """True when gemm_mx_rows takes a Linear layer under binding ab on the input x2d [M][K] (pre_act 2: [M][2K]) and gives the bits of
+    the two-launch route: a W4 MxActBinding, a Linear weight, K % 32 == 0, contiguous 16-byte aligned rows, no K split on the two-launch
+    route (MX_KSPLIT / its plan) and a plan for the shape.  n_sum: the columns of all problems of the launch (default: ab's)."""
+    if not (getattr(ab, "mx", False) and ab.w_bits == 4 and ab.pw.taps == 1 and x2d.dim() == 2):
+        return False
+    M, Kin = x2d.shape
+    K = Kin // 2 if pre_act == 2 else Kin
+    if not (ab.pw.K == K and K % 32 == 0 and M >= 1 and x2d.dtype in _lib.DTYPE_CODE and x2d.is_contiguous() and x2d.data_ptr() % 16 == 0):
+        return False
+    lib = _lib.load()
+    ksplit = lib.dgq_gemm_mx_plan_splits(M, ab.pw.N, ab.Kp, WORKSPACE_BYTES) if MX_KSPLIT is None else MX_KSPLIT
+    return ksplit == 1 and lib.dgq_gemm_mx_rows_plan(M, ab.pw.N if n_sum is None else n_sum, ab.Kp, ab.abits) != 0
+
+
+def gemm_mx_rows(x2d: torch.Tensor, bindings, pre=None, ln=None, extras=None, col_splits=None):
+    """[the layer of ab on x2d for ab in bindings] for 1 .. 4 W4 Linear layers under ONE real-time MX format (MxActBinding) that share the
+    input x2d [M][K] in ONE launch (dgq_gemm_mx_rows): each workgroup quantises its panel of rows in LDS with the block statement of
+    quant_act_mx6 / _mxint8 / _mx4 and walks its column tiles — the bits of _block_quant + _block_gemm un-split.  pre / ln: the folded
+    prologue as in quant_act; extras: a make_extra(...) or None per binding; col_splits: None = the plan's, an int = forced."""
+    who = "gemm_mx_rows"
+    assert x2d.dim() == 2 and x2d.is_contiguous() and x2d.dtype in _lib.DTYPE_CODE, who + ": x2d [M][K], contiguous"
+    assert 1 <= len(bindings) <= MX_ROWS_MAX_PROBLEMS, "%s: %d problems (1 .. %d)" % (who, len(bindings), MX_ROWS_MAX_PROBLEMS)
+    assert all(getattr(ab, "mx", False) and ab.w_bits == 4 for ab in bindings), who + ": every binding must be a W4 MxActBinding"
+    assert len({ab.fmt for ab in bindings}) == 1, who + ": the bindings must share one MX format"
+    M, Kin = x2d.shape
+    K = Kin // 2 if (pre and pre[2] == 2) else Kin
+    fmt = bindings[0].abits
+    a, keep = _quant_input(x2d, (M, 1, 1, K, 1, 1, 1, 0), fmt, pre, ln)
+    extras = list(extras) if extras is not None else [None] * len(bindings)
+    gs = (_lib.GemmArgs * len(bindings))()
+    outs = []
+    for g, ab, ex in zip(gs, bindings, extras):
+        pw = ab.pw
+        out = torch.empty((M, pw.N // 2 if (ex is not None and ex.geglu) else pw.N), dtype=x2d.dtype, device=x2d.device)
+        g.rowsum_parts, g.M, g.Kp, g.wpacked, g.w_bits, g.N, g.per_m, g.L = 1, M, ab.Kp, ab.wpacked.data_ptr(), 4, pw.N, 0, 1
+        g.alpha, g.gamma = pw.alpha.data_ptr(), ab.gamma.data_ptr()
+        g.y, g.y_dtype, g.ldy = out.data_ptr(), _lib.DTYPE_CODE[out.dtype], out.stride(0)
+        if ex is not None:
+            g.extra = _c.cast(_c.pointer(ex), _c.c_void_p)
+        outs.append(out)
+
+    def issue(_keep=(keep, list(bindings), extras, outs)):
+        _lib_call("dgq_gemm_mx_rows", _c.byref(a), fmt, len(bindings), _c.cast(gs, _c.c_void_p), 0 if col_splits is None else int(col_splits),
+                  _lib.stream())
+    issue()
+    if BLOCK_LAUNCH_HOOK is not None:
+        BLOCK_LAUNCH_HOOK(issue, "rows", (M, sum(ab.pw.N for ab in bindings), K))
+    return outs
+
+
 def quant_linear(x: torch.Tensor, ab: ActBinding, pre_act=0, residual=None, fq=None, ln=None, geglu=False):
     """x [..., K] -> [..., N].  pre_act: 0 none, 1 SiLU(x), 2 GEGLU (x is [..., 2K]: x[:K]·gelu(x[K:])) folded into the
     quantise-on-load pass; residual [..., N] and fq (see make_extra) folded into the GEMM epilogue.  geglu: the weight rows
@@ -1188,7 +1247,10 @@ def quant_linear(x: torch.Tensor, ab: ActBinding, pre_act=0, residual=None, fq=N
             res2 = res2.contiguous()
     if ab.block:                                         # real-time block mode: quantise the rows once, one GEMM
         geom = (rows, 1, 1, K, 1, 1, 1, 0)
-        y = _block_gemm(ab, _block_quant(ab, x2, geom, pre, ln, pad_k=True), geom, x.dtype, extra=make_extra(res2, fq, geglu=geglu))
+        if MX_ROWS_FUSED and mx_rows_ok(ab, x2, pre_act):   # ... or both in one launch: the same bits
+            y = gemm_mx_rows(x2, [ab], pre, ln, [make_extra(res2, fq, geglu=geglu)])[0]
+        else:
+            y = _block_gemm(ab, _block_quant(ab, x2, geom, pre, ln, pad_k=True), geom, x.dtype, extra=make_extra(res2, fq, geglu=geglu))
         return y.view(*x.shape[:-1], y.shape[-1])
     ab = _bind_rows(ab, x2, (rows, 1, 1, K, 1, 1, 1, 0), pre, ln)
     if pre_act != 2 and act_fuses(ab, rows, K, x.dtype, x2=x2):
@@ -1235,8 +1297,15 @@ def quant_linear_multi(x: torch.Tensor, bindings, ln=None):
     if any(ab.block for ab in bindings):                # real-time block layers: the shared input is quantised ONCE per bit width, one GEMM each
         geom = (M, 1, 1, Kin, 1, 1, 1, 0)
         quants, res = {}, {}
+        blk = [i for i, ab in enumerate(bindings) if ab.block]
+        chunks = [blk[j:j + MX_ROWS_MAX_PROBLEMS] for j in range(0, len(blk), MX_ROWS_MAX_PROBLEMS)]
+        if (MX_ROWS_FUSED and all(getattr(bindings[i], "mx", False) for i in blk) and len({bindings[i].fmt for i in blk}) == 1 and
+                all(mx_rows_ok(bindings[i], x2, n_sum=sum(bindings[k].pw.N for k in ch)) for ch in chunks for i in ch)):
+            for ch in chunks:                           # one MX format, every layer eligible: quantiser and GEMMs in one launch per 4 layers
+                for i, y in zip(ch, gemm_mx_rows(x2, [bindings[i] for i in ch], None, ln)):
+                    res[i] = y.view(*x.shape[:-1], y.shape[-1])
         for i, ab in enumerate(bindings):
-            if ab.block:
+            if ab.block and i not in res:
                 assert ab.pw.K == Kin and ab.pw.taps == 1
                 fmt = (ab.mx, ab.abits)                 # (one padded K per input width: every binding's Kp / 32 is the same)
                 if fmt not in quants:

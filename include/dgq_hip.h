@@ -57,7 +57,8 @@ extern "C" {
  *        dgq_conv2d_wq_mfma16_plan_splits, dgq_conv2d_wq_mfma16_workspace_bytes); the real-time MXFP4 mode, dgq_quant_act_mx4 /
  *        dgq_dequant_act_mx4 / dgq_gemm_mx4 / dgq_gemm_mx4_splitk with dgq_act_mx4_out_t and dgq_gemm_mx4_t; the K split of the
  *        real-time int block mode (dgq_gemm_blockq_splitk, dgq_gemm_blockq_plan_splits, dgq_gemm_blockq_workspace_bytes); the batch-row
- *        Linear layers of the MX modes in one launch (dgq_linear_smallm_mx_batch with dgq_smallm_mx_problem_t) — entries
+ *        Linear layers of the MX modes in one launch (dgq_linear_smallm_mx_batch with dgq_smallm_mx_problem_t); their general-M
+ *        Linear layers in one launch (dgq_gemm_mx_rows, dgq_gemm_mx_rows_plan) — entries
  *        added only, the revision stays 123 */
 #define DGQ_ABI_VERSION 123
 int dgq_version(void);
@@ -728,6 +729,20 @@ typedef struct dgq_smallm_mx_problem {
 } dgq_smallm_mx_problem_t;
 int dgq_linear_smallm_mx_batch(const void* x, int x_dtype, int M, int K, int64_t ldx, int pre_act, int a_format, int n_problems,
                                const dgq_smallm_mx_problem_t* probs, int y_dtype, void* stream);
+/* dgq_gemm_mx_rows: the general-M W4 Linear layer of the real-time MX modes in ONE launch — dgq_quant_act_mx6 / _mxint8 / _mx4 (a_format
+ * 6 / 8 / 4) on `in` and dgq_gemm_mx6 / _mxint8 / _mx4 un-split on each of the 1 .. 4 problems `probs` that share that input, with the
+ * codes and scale bytes formed per workgroup in LDS and never written to memory.  The result is bit-identical to those two launches.
+ * `in` is read as by dgq_quant_act_mx6 (x, x_dtype, B, H, W, C, bits, the folded prologue; 16-byte aligned, C % 32 == 0) and must be a
+ * Linear input: kh = kw = 1, no ups.  Of each problem M (= the input's rows), N, Kp, wpacked (dgq_pack_w_mx6's image), alpha, gamma, y,
+ * y_dtype (= x_dtype), ldy and extra are read, with the checks of dgq_gemm_mx6; `codes` is unused.  DGQ_EINVAL, nothing clamped: a padded K
+ * whose 32-row panel does not fit the 160 KiB of LDS (dgq_gemm_mx_rows_plan returns 0 for it), problems whose Kp or y_dtype differ, an
+ * extra with a conv / act descriptor or GroupNorm partials.  A workgroup owns a panel of 64 rows (32 where 64 do not fit: MXINT8
+ * beyond Kp = 1152) and 1 / col_splits of the column tiles of all problems; col_splits = 0: the plan's choice, >= 1: forced (clamped
+ * to the tiles; no split is empty) — the split changes no bit.  No atomics, no counters: deterministic, capture-safe.
+ * dgq_gemm_mx_rows_plan: the column splits the entry takes for M rows, Nsum columns in all and the padded K under a_format; 0 where the
+ * shape is not taken (the panel does not fit, one column tile in all). */
+int dgq_gemm_mx_rows(const dgq_quant_act_args_t* in, int a_format, int n_problems, const dgq_gemm_args_t* probs, int col_splits, void* stream);
+int dgq_gemm_mx_rows_plan(int M, int Nsum, int Kp, int a_format);
 
 /* ---- calibration producer --------------------------------------------------------
  * dgq_minmax_rows_cols: the statistics UniformAffineQuantizer.record_min_max_ema collects for DGQ's grouping

@@ -236,6 +236,38 @@ def mx_ksplit_table(torch, ops, dev, lines, fmt, sweep=(2, 4, 8, 16)):
     lines.append("largest plan workspace over these shapes: %.1f MB of ops.WORKSPACE_BYTES = %d MB" % (worst_ws / 2 ** 20, ops.WORKSPACE_BYTES >> 20))
 
 
+def mx_rows_table(torch, ops, dev, lines, fmt, sweep=(1, 2, 4, 8, 16)):
+    """the Linear layer of ``fmt`` in one launch (ops.gemm_mx_rows) against its quantiser + GEMM pair per SD Linear shape: the pair captured
+    twice (the spread of its own medians), forced column splits, the plan's choice; alternating rounds of hipGraph replays"""
+    from dgq_amd import _lib, synth
+    s_ = {"mxfp6": "mx6", "mxint8": "mxint8", "mxfp4": "mx4"}[fmt]
+    quant_mx, gemm_mx = getattr(ops, "quant_act_" + s_), getattr(ops, "gemm_" + s_)
+    lines += ["", "%s Linear layers, one launch (dgq_gemm_mx_rows) against quantiser + GEMM (fp32; 20 calls per hipGraph replay, median of 7 ALTERNATING"
+              % fmt.upper(), "rounds): the pair twice (pair, pair'), forced column splits, the plan's choice (0: shape not taken, then = pair)",
+              "%-28s %8s %8s %s %5s %8s %9s" % ("layer", "pair us", "pair' us", " ".join("%8s" % ("S=%d us" % s) for s in sweep), "plan", "plan us", "plan/pair")]
+    g = torch.Generator().manual_seed(0)
+    lib = _lib.load()
+    for name, geom, N, _ups in [r for r in KSPLIT_SHAPES if r[0].startswith("linear")]:
+        M, C = geom[0], geom[3]
+        w = torch.randn(N, C, generator=g) * C ** -0.5
+        wd, wz = synth.channel_minmax(w, 4)
+        mxb = ops.MxActBinding(ops.PackedWeight(w.to(dev), wd.to(dev), wz.to(dev), None, torch.zeros(N).to(dev), 4, C, 1), fmt)
+        x = (torch.randn(M, C, generator=g) * 1.3 + 0.2).to(dev)
+        plan = lib.dgq_gemm_mx_rows_plan(M, N, mxb.Kp, mxb.abits)
+        if lib.dgq_gemm_mx_rows_plan(M, 1 << 20, mxb.Kp, mxb.abits) == 0:       # the panel does not fit: nothing to time
+            lines.append("%-28s not taken (LDS)" % name)
+            continue
+        pair = lambda: captured(torch, lambda: gemm_mx(quant_mx(x, geom, lds=mxb.Kp // 32), geom, mxb, torch.float32))
+        graphs = {"a": pair(), "b": pair()}
+        graphs.update({s: captured(torch, lambda s=s: ops.gemm_mx_rows(x, [mxb], col_splits=s)) for s in sweep})
+        if plan:
+            graphs["plan"] = captured(torch, lambda: ops.gemm_mx_rows(x, [mxb]))
+        us = alternating_us(torch, graphs)
+        pl = us.get("plan", us["a"])
+        lines.append("%-28s %8.2f %8.2f %s %5d %8.2f %9.3f" % (name, us["a"], us["b"], " ".join("%8.2f" % us[s] for s in sweep), plan, pl, pl / us["a"]))
+        del graphs
+
+
 def mxw8_kernel_table(torch, ops, dev, lines, fmt):
     """dgq_gemm_mxw8 under ``fmt`` activations, by the plan's K split as the layers run it, against dgq_gemm_blockq at W8 and the same bit
     width (captured twice), with both quantisers, per SD layer shape of mx_kernel_table"""
@@ -532,6 +564,7 @@ def main(argv=None):
     ap.add_argument("--mxint8", action="store_true", help="measure the real-time MXINT8 mode (see the head of this file)")
     ap.add_argument("--mx-ksplit", action="store_true", help="measure the K split of the two MX GEMMs: per shape, and (without --kernels-only) per step")
     ap.add_argument("--mx-w8", action="store_true", help="measure W8 layers under both MX formats, flag on against flag off (see the head of this file)")
+    ap.add_argument("--mx-rows", action="store_true", help="measure the one-launch Linear layers of the MX modes (ops.MX_ROWS_FUSED): per shape, and (without --kernels-only) per step")
     ap.add_argument("--append", default=None, help="--mx / --mxint8: a text file whose lines are appended to the report (the tests' measured constants)")
     args = ap.parse_args(argv)
     import torch
@@ -548,6 +581,30 @@ def main(argv=None):
         for fmt, ab in (() if args.kernels_only else (("mxfp6", 6), ("mxint8", 8))):
             modes = (("off", "%s asked, flag off (int blocks, A%d)" % (fmt.upper(), ab)), ("on", "%s, real_time_mx_w8=True" % fmt.upper()), ("off#2", "flag off, second slot"))
             mx_step_table(torch, ops, args, dev, lines, modes, ab, build=lambda m: build_rt_model(torch, "sd", fmt, ab, 50, 2, 64, dev, wbits=8, mx_w8=m == "on"), wbits=8)
+            lines.append("per round (ms), off | on | off#2: " + "; ".join("%.3f | %.3f | %.3f" % p for p in zip(*args.rounds_log)))
+            ops._WORKSPACE.clear()
+            gc.collect()
+            torch.cuda.empty_cache()
+        if args.append:
+            lines += [""] + open(args.append).read().splitlines()
+        text = "\n".join(lines) + "\n"
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text)
+        print(text)
+        return 0
+    if args.mx_rows:
+        lines = ["One-launch Linear layers of the real-time MX modes (dgq_gemm_mx_rows, ops.MX_ROWS_FUSED) — tools/profile_realtime_act.py --mx-rows",
+                 "commit %s; %s; torch %s; ABI %d" % (args.stamp or stamp_default(), torch.cuda.get_device_name(0), torch.__version__, _lib.ABI_VERSION)]
+        for fmt in ("mxfp6", "mxint8", "mxfp4"):
+            mx_rows_table(torch, ops, dev, lines, fmt)
+        for fmt, ab in (() if args.kernels_only else (("mxfp4", 4), ("mxfp6", 6))):
+            def build(m, fmt=fmt, ab=ab):
+                ops.MX_ROWS_FUSED = m == "on"               # read at capture, right behind the build
+                return build_rt_model(torch, "sd", fmt, ab, 50, 2, 64, dev)
+            modes = (("off", "%s, MX_ROWS_FUSED off" % fmt.upper()), ("on", "%s, MX_ROWS_FUSED on" % fmt.upper()), ("off#2", "off, second slot"))
+            mx_step_table(torch, ops, args, dev, lines, modes, ab, build=build)
+            ops.MX_ROWS_FUSED = False
             lines.append("per round (ms), off | on | off#2: " + "; ".join("%.3f | %.3f | %.3f" % p for p in zip(*args.rounds_log)))
             ops._WORKSPACE.clear()
             gc.collect()
